@@ -10,9 +10,12 @@ timed region starts.  One process per GPU; for N>1 the driver launches this file
 ``torch.distributed.run`` and the ranks shard the global batch (independent samples, no data-path
 collective); timing = max over ranks of K steps bracketed by barrier + synchronize.
 
-Prints ONE JSON line (rank 0) with the driver contract plus ``roofline`` (dominant kernel, HIP-event
-timed on the launch stream inside this run) and ``cpu_baseline`` (the CPU oracle, a port of the
-reference's PyTorch op graph, timed on a bounded sample on this host's cores).
+Prints ONE JSON line (rank 0) with the driver contract.  A plain run sets up, warms up, times the K
+steps and prints the line; ``--full`` adds what takes runs of its own: ``roofline`` (dominant kernel,
+HIP-event timed on the launch stream inside this run), ``cpu_baseline`` (the CPU oracle, a port of the
+reference's PyTorch op graph, timed on a bounded sample on this host's cores) with the oracle parity,
+the host submission pass and the single-rank extras.  ``--dump-outputs DIR`` writes the timed path's
+last export as ``.npy`` files.
 """
 import argparse
 import json
@@ -477,7 +480,7 @@ def encoder_mfma_busy():
 def secondary(config, with_cpu=True):
     """BASELINE.json configs[1] / configs[2] (parity-test cases, NOT the driver's metric): IHMR-Baseline batch 64 and
     IHMR-MLP batch 128 inference on one MI355X with the CPU oracle timed beside them on a bounded sample (BASELINE.md
-    section 3: "reported per config").  Returned as a dict: the default run attaches both to its line under
+    section 3: "reported per config").  Returned as a dict: a `--full` run attaches both to its line under
     `secondary_configs` (so that a driver record exists for them); `python bench.py --config baseline|mlp` prints one alone."""
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -694,6 +697,33 @@ def secondary(config, with_cpu=True):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(res, out_dir, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """`--dump-outputs DIR`: the export dict the timed path handed back in its last step -> DIR/<name>.npy (float32 arrays as they are,
+    everything else as float64).  Every array of the export holds one row per sample (leading axis, as `do_flip`); an array that does not
+    is an error, not a guess.  The files in all -- .npy headers and DIR/sample_rows.npy included -- stay within `max_bytes`: above it the
+    same fixed seeded sample of rows is kept of every array and the row numbers go to DIR/sample_rows.npy; a cap that not even one row
+    fits raises."""
+    arrays = {k: np.array(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in res.items()}
+    n = len(next(iter(arrays.values())))
+    assert all(a.ndim and a.shape[0] == n for a in arrays.values()), {k: a.shape for k, a in arrays.items()}
+    header = 256                                      # bytes reserved per .npy header (numpy writes 128 for these shapes)
+    data = sum(a.nbytes for a in arrays.values())
+    if data + header * len(arrays) > max_bytes:
+        per_row = data / n + 8                        # + the row's float64 entry in sample_rows.npy
+        keep = int((max_bytes - header * (len(arrays) + 1)) // per_row)
+        if keep < 1:
+            raise ValueError(f"--dump-outputs: one sample ({per_row:.0f} bytes) does not fit in {max_bytes} bytes")
+        rows = np.sort(np.random.RandomState(seed).choice(n, min(keep, n), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: start N ranks of this file under `torch.distributed.run` as a CHILD process
     (never an exec, and nothing in this parent has initialised the GPU: `torch.cuda.device_count()` does not on this image) and
@@ -741,11 +771,21 @@ def main():
                          "all-reduce) on device tensors through the process group's backend and report the checks in the line")
     ap.add_argument("--asset", type=str, default="mitten", choices=["mitten", "fingers"],
                     help="synthetic MANO-shaped model of the run: the default blob, or the five-finger mesh with interlocked batches "
-                         "(geometry sensitivity; the default run reports both under `geometry`)")
+                         "(geometry sensitivity; a --full run reports both under `geometry`)")
     ap.add_argument("--config", type=str, default="opt", choices=["opt", "baseline", "mlp"],
                     help="opt = the driver's bench line (IHMR-OPT); baseline / mlp = one of the secondary BASELINE.json configs alone")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: host submission pass, kernel rooflines, CPU baseline + oracle parity, and (one "
+                         "rank) the extras of --no-extras.  Without it the run sets up, warms up, times --steps and prints the line.  Applies to "
+                         "the IHMR-OPT line: --config baseline|mlp is itself one of these extra measurements and runs as it always has")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step (the export of the last launch "
+                         "sequence) as DIR/<name>.npy, float32 / float64, at most 64 MB (a fixed seeded sample of the rows beyond that); "
+                         "IHMR-OPT line only")
     args = ap.parse_args()
     if args.config != "opt":
+        if args.dump_outputs:
+            sys.exit("bench.py: --dump-outputs writes the IHMR-OPT line's outputs; --config baseline|mlp has none to write")
         assert torch.cuda.is_available(), "bench.py needs an MI355X: the hot path has no CPU fallback"
         print(json.dumps(secondary(args.config, with_cpu=not args.no_cpu_baseline)))
         return
@@ -841,12 +881,12 @@ def main():
                 m.get_pred_result_async().wait(); m.get_pred_result_async().wait()
         return pool[(i, g)]
 
-    def run_steps(n, src=inputs):
+    def run_steps(n, src=inputs, sizes=None):
         """n full passes over one batch each (set_input -> init_optimize -> optimize -> get_pred_result), S streams x up to
         G fused batches in flight.  `src` = the device-resident inputs, or the pinned host copies (then every step's 15
         input tensors cross PCIe inside the step, as in the reference's loop body)."""
         res = None
-        sizes = plan(n)
+        sizes = plan(n) if sizes is None else sizes
         pending = []                               # export handles of the previous round
         t_wait = 0.0                               # host time spent WAITING for the GPU (export handles): everything else is submission
         t_begin = time.perf_counter()
@@ -877,7 +917,7 @@ def main():
         host_submit[0] = (time.perf_counter() - t_begin - t_wait) / max(n, 1)
         return res
 
-    extras = rank == 0 and world == 1 and not args.no_extras
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras
     needs_single = extras or any(g == 1 for n in (max(args.warmup, 0), args.steps) for q in plan(n) for g in q)
     if needs_single:                                 # the pre-built single-batch instance gets its untimed first pass too (profiling
         with torch.cuda.stream(streams[0]):          # runs without a one-batch job skip it: its launches would blur the per-kernel means)
@@ -909,16 +949,22 @@ def main():
         return dt, r
 
     run_steps(max(args.warmup, 0))
+    # every launch sequence size the timed region runs, once per stream and interleaved as there, right before it: the warm-up's own
+    # sequences are smaller (5 steps = 2 + 2 + 1 batches against 7 + 7 + 6 for 20), and a timed window entered cold reads ~2 % low.
+    # At most two sizes per stream whatever --steps is, so this stays a fraction of a second
+    run_steps(0, sizes=[sorted(set(q), reverse=True) for q in plan(args.steps)])
     # ---- host submission cost (what decides whether N ranks x S streams scale on one node's CPUs): the SAME K steps with the GPU
     #      synchronised out of the picture as far as the loop allows -- the thread's wall time minus its waits for export handles.
-    #      Measured on a pass of its own so that the timed region below stays exactly the contract's
-    run_steps(args.steps)
-    torch.cuda.synchronize()
-    submit_ms = 1000.0 * host_submit[0]
-    if dist is not None:
-        t = torch.tensor([submit_ms], device="cuda", dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        submit_ms = float(t.item())
+    #      Measured on a pass of its own (--full) so that the timed region below stays exactly the contract's
+    submit_ms = None
+    if args.full:
+        run_steps(args.steps)
+        torch.cuda.synchronize()
+        submit_ms = 1000.0 * host_submit[0]
+        if dist is not None:
+            t = torch.tensor([submit_ms], device="cuda", dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            submit_ms = float(t.item())
     # (experiment builds only, -DIHMR_TIMELINE + IHMR_TIMELINE_OUT=<file.npy>: workgroup records of the timed region, scripts/timeline_wg.py)
     tl_out = os.environ.get("IHMR_TIMELINE_OUT") if hasattr(hip.lib(), "ihmr_debug_timeline") else None
     if tl_out:
@@ -930,6 +976,9 @@ def main():
         rec = np.zeros((4 << 20, 3), np.uint64)
         n_rec = hip.lib().ihmr_debug_timeline(rec.ctypes.data, 0)
         np.save(tl_out, rec[:max(n_rec, 0)])
+    # the arrays are views of the instance's pinned export buffers: written now, before any --full pass reuses them
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res, args.dump_outputs)
     ms_per_step = 1000.0 * elapsed / args.steps
     value = world * B * args.steps / elapsed
     # the same K steps with the per-step host-to-device copy of the inputs inside the timed region (never `value`)
@@ -946,7 +995,7 @@ def main():
     #      timed region actually ran (with several sequences in flight the kernels share the GPU and a per-launch time is
     #      meaningless); work and algorithmic bytes from the collision kernels' own counters in a second, untimed pass
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         roofline = kernel_rooflines(args, B, plan, instance, inputs, hip)
 
     # ---- single-batch latency: ONE batch of --batch samples, one stream, nothing else in flight.
@@ -1056,7 +1105,7 @@ def main():
         geometry.append(dict(throughput_ratio_fingers_over_mitten=geometry[1]["images_per_s"] / geometry[0]["images_per_s"]))
 
     cpu, parity = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.asset == "mitten":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.asset == "mitten":
         cpu, oracle_out = cpu_baseline(batch_cpu, args.epoch, freq)
         parity = parity_vs_oracle(batch_cpu, oracle_out, -1)
     second = None
@@ -1097,7 +1146,8 @@ def main():
             ms_per_refine_iter_amortised=amortised, higher_is_better=True, scaling="weak", vs_baseline=None,
             # multi-GPU readiness measurable on one GPU: the launch thread's work per step (max over ranks).  A rank keeps its GPU fed
             # as long as this stays below the GPU time of a step (ms_per_step of a one-GPU run: on 8 GPUs every rank has its own)
-            host_submit_ms_per_step=submit_ms, host_submit_fraction_of_step=submit_ms / ms_per_step if world == 1 else None,
+            host_submit_ms_per_step=submit_ms,
+            host_submit_fraction_of_step=submit_ms / ms_per_step if (world == 1 and submit_ms is not None) else None,
             host_cpu_affinity=numa_pin,
             dtype="f32", data="synthetic",
             config=dict(workload=f"IHMR-OPT opt_default epoch={args.epoch} ({n_iters} refine iterations + final forward), "
@@ -1112,7 +1162,7 @@ def main():
                         devices_visible=torch.cuda.device_count(), ranks_per_device=-(-world // max(torch.cuda.device_count(), 1)),
                         dist_backend=(dist.get_backend() if dist is not None else None),
                         # the metric's second half -- ms per refinement iteration at batch 64 with ONE batch in flight -- copied
-                        # here from `latency` because the driver's record keeps `config` (null in --no-extras / multi-rank runs)
+                        # here from `latency` because the driver's record keeps `config` (null without --full, with --no-extras, multi-rank)
                         latency_ms_per_refine_iter=latency["ms_per_refine_iter"] if latency else None,
                         latency_images_per_s=latency["images_per_s"] if latency else None,
                         latency_stage_us_per_refine_iter=latency["stage_us_per_refine_iter"] if latency else None,

@@ -25,7 +25,7 @@ def _run(args, timeout=600, nproc=2, backend="gloo"):
 
 
 def test_bench_with_two_ranks_prints_one_line():
-    lines = _run(["bench.py", "--gpus", "2", "--steps", "8", "--warmup", "4"])
+    lines = _run(["bench.py", "--gpus", "2", "--steps", "8", "--warmup", "4", "--full"])
     assert len(lines) == 1
     d = lines[0]
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 128 and d["steps"] == 8 and d["scaling"] == "weak"
@@ -37,7 +37,7 @@ def test_bench_gpus_2_without_a_launcher_starts_two_ranks():
     two ranks (a child `torch.distributed.run`, before the parent touches the GPU) and pass their one line through -- n_gpus 2, the
     whole job's batch.  On this one-GPU box the two ranks share the device over gloo and the line says so."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "IHMR_DIST_BACKEND")}
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "8", "--warmup", "4"], cwd=ROOT, env=env,
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "8", "--warmup", "4", "--full"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
@@ -55,7 +55,7 @@ def test_bench_gpus_2_without_a_launcher_starts_two_ranks():
 def test_bench_line_keeps_the_latency_figures_in_config():
     """The metric's second half (ms per refinement iteration at batch 64, one batch in flight) and the per-stage figures sit in
     `config`, which the driver's record keeps."""
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "6", "--warmup", "3", "--no-cpu-baseline", "--no-work-counters"],
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "6", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-work-counters"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -65,6 +65,36 @@ def test_bench_line_keeps_the_latency_figures_in_config():
     assert len(c["latency_stage_us_per_refine_iter"]) == 4 and all(10.0 < x < 300.0 for x in c["latency_stage_us_per_refine_iter"])
     assert c["distinct_batches"] == max(g for q in c["launch_sequences_timed"] for g in q) == 2 and d["parity"]["translated_reuse"] == "on"
     print(f"[bench] latency {c['latency_ms_per_refine_iter']:.4f} ms per iteration, stages {c['latency_stage_us_per_refine_iter']}")
+
+
+def test_plain_bench_run_is_lean_and_dumps_identical_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and carries none of the separate passes; two runs with the same arguments
+    dump the same inputs and bit-identical outputs of the timed path's last step."""
+    import numpy as np
+    import time
+    lines, walls = [], []
+    for d in ("a", "b"):
+        t0 = time.perf_counter()
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path / d)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=600)
+        walls.append(time.perf_counter() - t0)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    for d, wall in zip(lines, walls):
+        # the whole process outside its (steps + warmup) steps -- start-up, set-up, graph capture, the dump -- stays within 30 s
+        outside = wall - (d["steps"] + d["warmup"]) * d["ms_per_step"] / 1000.0
+        print(f"[bench] plain run: {wall:.2f} s wall, {outside:.2f} s outside the steps")
+        assert outside < 30.0, outside
+        assert d["steps"] == 4 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["unit"] == "images/s" and d["dtype"] == "f32"
+        assert abs(d["value"] - 64 * 1000.0 / d["ms_per_step"]) < 1e-6 * d["value"]
+        assert sum(sum(q) for q in d["config"]["launch_sequences_timed"]) == 4
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["latency"] is None and d["host_submit_ms_per_step"] is None
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "pred_right_hand_verts.npy" in names and "gt_joints_3d.npy" in names
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and np.array_equal(a, b), f
+    assert np.isfinite(np.load(tmp_path / "a" / "pred_right_hand_verts.npy")).all()
 
 
 def test_run_optimize_two_ranks_equals_one_process():
@@ -83,7 +113,7 @@ def test_bench_with_eight_ranks_runs_config_5_code_path():
     # capturing their graphs at once -- has read 7.8 ms where every later run reads 0.3 - 0.6; the run is repeated once before the bound counts.
     # Everything else is asserted on every run.)
     for attempt in range(2):
-        lines = _run(["bench.py", "--gpus", "8", "--steps", "8", "--warmup", "3"], nproc=8, timeout=1500)
+        lines = _run(["bench.py", "--gpus", "8", "--steps", "8", "--warmup", "3", "--full"], nproc=8, timeout=1500)
         assert len(lines) == 1
         d = lines[0]
         assert d["n_gpus"] == 8 and d["config"]["global_batch"] == 512 and d["steps"] == 8 and d["warmup"] == 3 and d["scaling"] == "weak"
@@ -101,7 +131,7 @@ def test_host_submission_cost_is_a_fraction_of_a_step():
     """One rank: the launch thread's work per step (graph launches, input staging, export requests; bench.py:
     host_submit_ms_per_step) against the step's GPU time."""
     for attempt in range(2):       # (a timing bound: repeated once, see the eight-rank test)
-        r = subprocess.run([sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-extras", "--no-work-counters"],
+        r = subprocess.run([sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-extras", "--no-work-counters"],
                            cwd=ROOT, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -3,6 +3,7 @@ import os
 import sys
 import types
 import numpy as np
+import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -210,6 +211,37 @@ def test_bench_quotes_only_profiles_of_the_loaded_library(monkeypatch):
     assert bench.committed_profile(None, None) == (None, None)
 
 
+def test_bench_dump_outputs_writes_float_arrays_within_the_cap(tmp_path):
+    """`bench.py --dump-outputs DIR`: one float32 / float64 .npy per exported array; above the byte cap the same fixed seeded rows
+    are kept of every per-sample array (their row numbers beside them), identically on every call."""
+    import bench
+    rng = np.random.RandomState(3)
+    n = 100
+    res = dict(pred_right_hand_verts=rng.rand(n, 778, 3).astype(np.float32), collision_loss=rng.rand(n).astype(np.float32),
+               do_flip=np.zeros(n, np.int32))
+    bench.dump_outputs(res, str(tmp_path / "all"))
+    for k, v in res.items():
+        a = np.load(tmp_path / "all" / f"{k}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, v.astype(a.dtype)), k
+    assert not (tmp_path / "all" / "sample_rows.npy").exists()
+    cap = 200_000
+    for d in ("a", "b"):
+        bench.dump_outputs(res, str(tmp_path / d), max_bytes=cap)
+    rows = np.load(tmp_path / "a" / "sample_rows.npy").astype(np.int64)
+    assert 1 <= len(rows) < n and np.array_equal(rows, np.load(tmp_path / "b" / "sample_rows.npy"))
+    for k, v in res.items():
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert np.array_equal(a, b) and np.array_equal(a, v[rows].astype(a.dtype)), k
+    # the cap holds for the files on disk, headers and the row numbers included, and is used: one more row would not fit
+    on_disk = sum(f.stat().st_size for f in (tmp_path / "a").iterdir())
+    per_row = sum(v.astype(np.float32 if v.dtype == np.float32 else np.float64).nbytes for v in res.values()) / n + 8
+    assert on_disk <= cap and on_disk + per_row > cap - 256 * (len(res) + 1), (on_disk, cap)
+    with pytest.raises(ValueError):                   # not even one sample fits: refused, never silently over the cap
+        bench.dump_outputs(res, str(tmp_path / "c"), max_bytes=5000)
+    with pytest.raises(AssertionError):               # an array that is not one row per sample is not sampled by guess
+        bench.dump_outputs(dict(res, extra=np.zeros(7, np.float32)), str(tmp_path / "d"), max_bytes=cap)
+
+
 def test_committed_profiles_belong_to_the_committed_sources():
     """The final-code profile series of the round was taken from exactly the sources in the tree (hash of csrc/ + the header + the
     hipcc flags), so the driver's bench line can quote it."""
@@ -286,6 +318,20 @@ def test_committed_profile_carries_what_the_bench_line_quotes():
     assert 2e7 < traffic < 5e8 and 10.0 < us < 200.0 and 1e6 < inst < 1e8
     # issue slots at the peak clock (bench.py: roofline.valu.issue_slots): a fraction of one
     assert 0.05 < inst * 3.0 / (1024.0 * us * 1e-6 * 2.4e9) < 1.0
+
+
+def test_design_numbers_refuses_a_plain_bench_line(tmp_path):
+    """scripts/design_numbers.py quotes roofline and host-submission figures that only `bench.py --full` measures: a plain line (those
+    fields null) is refused with a message, not turned into a TypeError or a section of zeros."""
+    import json as _json
+    sys.path.insert(0, os.path.join(ROOT, "scripts"))
+    import design_numbers
+    d = _json.loads([l for l in open(os.path.join(ROOT, "profiles", "r6_v4_bench_line.json")).read().splitlines() if l.startswith("{")][-1])
+    d.update(roofline=None, host_submit_ms_per_step=None, host_submit_fraction_of_step=None, latency=None, cpu_baseline=None)
+    f = tmp_path / "plain_bench_line.json"
+    f.write_text(_json.dumps(d) + "\n")
+    with pytest.raises(SystemExit, match="--full"):
+        design_numbers.block(str(f))
 
 
 def test_design_section_6_is_generated_from_the_committed_bench_line():
