@@ -20,18 +20,29 @@ wrist-to-wrist translation is a few centimetres.
 from __future__ import annotations
 
 import math
-from typing import Callable, Dict
+from typing import Callable, Dict, Optional
 
 import numpy as np
 import torch
 
+DEEP_TRANS = 0.005      # metres: half-width of the deep-overlap batch's translation box
+
 
 def synthetic_opt_batch(batch_size: int, forward_fn: Callable, seed: int = 1234, first_index: int = 0,
-                        with_image: bool = False, with_feat: bool = False, interlock: bool = False) -> Dict[str, torch.Tensor]:
+                        with_image: bool = False, with_feat: bool = False, interlock: bool = False,
+                        overlap: Optional[str] = None) -> Dict[str, torch.Tensor]:
     """``interlock`` (for the finger asset, ``assets.synthetic_mano(kind="fingers")``): instead of two hands lying on each other, the
     left hand keeps its native direction (the mirrored model points to -x) and comes from the front, its wrist ~26 cm ahead of the
     right wrist and half a finger pitch to the side: the fingers of one hand sit between -- and, with the random pose noise, in --
-    the fingers of the other.  Same random draws as the default batch (which is unchanged), other means."""
+    the fingers of the other.  Same random draws as the default batch (which is unchanged), other means.
+
+    ``overlap="deep"``: deeply interpenetrating hands -- the wrist-to-wrist translation is drawn from ``U(-DEEP_TRANS, DEEP_TRANS)^3``
+    around zero instead of around the 3.4 cm z offset, so the half-turned left hand lies almost on the right one.  Same random draws
+    as the default batch, another mean and spread of the translation only."""
+    if overlap not in (None, "deep"):
+        raise ValueError(f"overlap must be None or 'deep', not {overlap!r}")
+    if overlap is not None and interlock:
+        raise ValueError("overlap and interlock are two different geometries")
     rng = np.random.RandomState(seed)
     B = batch_size
     f32 = np.float32
@@ -41,8 +52,10 @@ def synthetic_opt_batch(batch_size: int, forward_fn: Callable, seed: int = 1234,
     init_pose[:, 0:3] = rng.normal(0.0, 0.1, size=(B, 3)).astype(f32)
     init_shape = rng.normal(0.0, 0.5, size=(B, 20)).astype(f32)
     init_cam = (np.array([5.0, 0.0, 0.0]) + rng.normal(0.0, 0.05, size=(B, 3))).astype(f32)
-    init_trans = (rng.uniform(-1.0, 1.0, size=(B, 3)) * np.array([0.02, 0.02, 0.012])
-                  + np.array([0.0, 0.0, 0.034])).astype(f32)
+    u_trans = rng.uniform(-1.0, 1.0, size=(B, 3))
+    init_trans = (u_trans * np.array([0.02, 0.02, 0.012]) + np.array([0.0, 0.0, 0.034])).astype(f32)
+    if overlap == "deep":
+        init_trans = (u_trans * DEEP_TRANS).astype(f32)
     if interlock:
         init_pose[:, 48:51] -= np.array([0.0, 0.0, 0.97 * math.pi], f32)          # no half turn: the left hand points at the right one
         init_trans = (init_trans - np.array([0.0, 0.0, 0.034], f32)) * np.array([1.0, 0.5, 0.5], f32) + np.array([0.26, 0.009, 0.002], f32)

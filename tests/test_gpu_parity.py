@@ -132,25 +132,11 @@ def test_lbs_dense_weight_asset_matches_oracle(mano_arrays):
 
 
 # ----------------------------------------------------------------------------------- seam B (collision)
-def _two_hand_verts(mano_arrays, B, seed, interlock=False):
-    """(B,2,778,3) penetrating hand pairs from the oracle forward on the synthetic batch (interlock: the finger asset's batch generator)."""
-    from oracle.opt_ref import OptimizeRef
-    from ihmr_amd.synthetic import synthetic_opt_batch
-    right, left = mano_arrays
-    orc = OptimizeRef(right, left, B, [], save_mid_freq=1)
-
-    def fwd(pose, shape, trans):
-        orc.pred_right_orient, orc.pred_left_orient = pose[:, :3], pose[:, 48:51]
-        orc.pred_right_pose_params, orc.pred_left_pose_params = pose[:, 3:48], pose[:, 51:]
-        orc.pred_right_shape_params, orc.pred_left_shape_params = shape[:, :10], shape[:, 10:]
-        orc.pred_hand_trans = trans.view(-1, 1, 3)
-        fwd.out = orc.get_mano_output()
-        return fwd.out[2]
-
-    batch = synthetic_opt_batch(B, fwd, seed=seed, interlock=interlock)
-    fwd(batch["init_pose_params"], batch["init_shape_params"], batch["init_hand_trans"][:, 0, :3])
-    rv, lv, _ = fwd.out
-    return torch.stack([rv, lv], dim=1).contiguous(), batch
+def _two_hand_verts(mano_arrays, B, seed, interlock=False, overlap=None):
+    """(B,2,778,3) penetrating hand pairs from the oracle forward on the synthetic batch (interlock: the finger asset's batch generator;
+    overlap="deep": the deeply interpenetrating batch, tests/helpers.py)."""
+    from helpers import oracle_two_hand_verts
+    return oracle_two_hand_verts(mano_arrays, B, seed, interlock=interlock, overlap=overlap)
 
 
 @pytest.mark.parametrize("squash", [None, 0.3, 1e-3, 1e-6, "ball"], ids=["hands", "flat", "thin", "sliver", "ball"])
@@ -286,6 +272,74 @@ def test_sdf_disjoint_hands_zero(mano_arrays):
     assert float(l.abs().max()) == 0.0 and float(pv.abs().max()) == 0.0
 
 
+# ----------------------------------------------------------------------------------- seam B under deep interpenetration
+def _deep_pairs(mano_arrays, geometry, B):
+    """The deep batch's initial hand pairs, or ("point cloud") the same with the left hand replaced by a point cloud over the right hand's
+    box: the geometries tests/test_collision_geometry_cpu.py shows to reach the second ray-queue window and the long candidate lists."""
+    from helpers import DEEP_SEED, POINT_CLOUD_SEED, point_cloud_pairs
+    hv, batch = _two_hand_verts(mano_arrays, B, DEEP_SEED, overlap="deep")
+    return (point_cloud_pairs(hv, POINT_CLOUD_SEED) if geometry == "point cloud" else hv), batch
+
+
+@pytest.mark.parametrize("geometry,B", [("deep", 8), ("deep", 96), ("point cloud", 8)])
+def test_sdf_collision_matches_oracle_under_deep_overlap(mano_arrays, geometry, B):
+    """Seam B against the oracle on deeply interpenetrating pairs, with test_sdf_collision_matches_oracle's tolerances.  B = 96 is 192
+    hands: more than SDF_PREP_SMALL_MAX_HANDS = 128, so the 512-thread form of the prep kernel runs.  The point cloud needs almost every
+    column of the right hand's grid (tens of thousands of ray-queue pairs, many SDF_RAYQ windows), and its own 'mesh' is a tangle of
+    long triangles whose ray parity must still be the oracle's bit for bit."""
+    from helpers import needed_voxels, ray_queue_pairs
+    from ihmr_amd.sdf import SDFLoss
+    from oracle.sdf_ref import SDFLossRef
+    right, left = mano_arrays
+    hv, _ = _deep_pairs(mano_arrays, geometry, B)
+    P = ray_queue_pairs(hv, right["faces"], left["faces"], needed_voxels(hv))
+    print(f"[parity] {geometry} B={B}: ray-queue pairs per hand max {P.max()}, hands over 3072: {int((P > 3072).sum())} of {P.size}")
+    ref_mod = SDFLossRef(right["faces"], left["faces"])
+    hv_ref = hv.clone().requires_grad_(True)
+    l_ref, pv_ref, os_ref = ref_mod(hv_ref, return_per_vert_loss=True, return_origin_scale_loss=True)
+    w = torch.linspace(0.5, 1.5, B)
+    (l_ref * w).sum().backward()
+    mod = SDFLoss(right["faces"], left["faces"]).to(_dev())
+    hv_g = hv.clone().to(_dev()).requires_grad_(True)
+    l, pv, os_ = mod(hv_g, return_per_vert_loss=True, return_origin_scale_loss=True)
+    (l * w.to(_dev())).sum().backward()
+    print(f"[parity] {geometry} B={B}: penetrating vertices (ref) {int((pv_ref > 0).sum())}, mean loss {float(l_ref.detach().mean()):.4f}")
+    assert int((pv_ref > 0).sum()) > 300 * B, "the pairs must penetrate deeply"
+    _report(f"{geometry} B={B} sdf per_vert", pv.detach().cpu(), pv_ref.detach(), atol=1e-6)
+    _report(f"{geometry} B={B} sdf origin_scale [m]", os_.detach().cpu(), os_ref.detach(), atol=1e-7)
+    _report(f"{geometry} B={B} sdf loss", l.detach().cpu(), l_ref.detach(), atol=1e-5, rtol=1e-6)
+    _report(f"{geometry} B={B} sdf d/dverts", hv_g.grad.cpu(), hv_ref.grad, atol=1e-4 * float(hv_ref.grad.abs().max()))
+
+
+@pytest.mark.parametrize("B", [64, 96])
+def test_sdf_inside_bits_match_the_oracle_grid_under_deep_overlap(mano_arrays, B):
+    """The fused loop's collision launch on the deep batch (set_input, init_optimize, forward_losses): the inside-voxel bitmaps it leaves
+    in the workspace equal, bit for bit, the oracle's float32 grid > 0 on the voxels the other hand's vertices read (and nothing else),
+    computed on the very vertices the launch saw; the boxes equal the oracle's (centre, scale).  B = 96: the 512-thread prep form."""
+    from helpers import DEEP_SEED, needed_voxels, oracle_inside
+    from ihmr_amd.optimize_model import OptimizeModel
+    from oracle.sdf_ref import hand_boxes
+    right, left = mano_arrays
+    _, batch = _two_hand_verts(mano_arrays, B, DEEP_SEED, overlap="deep")
+    model = OptimizeModel(_make_opt(B, epoch=2, save_mid_freq=1))
+    model.set_input(batch); model.init_optimize(); model.forward_losses()
+    torch.cuda.synchronize()
+    bits, box = model.sdf_inside_bits()
+    hv = torch.stack([model.buf["verts"][0], model.buf["verts"][1]], dim=1).cpu().contiguous()
+    want = needed_voxels(hv) & oracle_inside(hv, right["faces"], left["faces"])           # (B,2,k,j,i)
+    words = (want.astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(-1).astype(np.uint32).reshape(B, 2, 1024)
+    words = words.transpose(1, 0, 2)                                                       # (hand, sample, k * 32 + j): bit i
+    n_want = int(want.sum())
+    n_got = int(sum(bin(int(x)).count("1") for x in bits[bits != 0]))
+    n_diff = int(sum(bin(int(x)).count("1") for x in (bits ^ words)[(bits ^ words) != 0]))
+    print(f"[parity] deep B={B}: inside voxels read per hand (oracle) {n_want / (2 * B):.1f}, got {n_got / (2 * B):.1f}; voxels that differ {n_diff}")
+    assert n_want > 300 * 2 * B
+    assert n_diff == 0
+    centre, scale = hand_boxes(hv)
+    ref_box = torch.cat([centre[:, :, 0, :], scale[:, :, 0, :]], dim=-1).transpose(0, 1).numpy()
+    assert np.array_equal(box, ref_box), float(np.abs(box - ref_box).max())
+
+
 # ----------------------------------------------------------------------------------- seam C (OPT loop)
 def _make_opt(B, strategy="opt_default", epoch=4, save_mid_freq=2, model_root=""):
     import types
@@ -295,14 +349,14 @@ def _make_opt(B, strategy="opt_default", epoch=4, save_mid_freq=2, model_root=""
                                  optimizer="adam", opt_epoch=epoch)
 
 
-def _oracle_and_model(mano_arrays, B, epoch, freq, seed=1234, record=True, fingers=False):
+def _oracle_and_model(mano_arrays, B, epoch, freq, seed=1234, record=True, fingers=False, overlap=None):
     """fingers: `mano_arrays` is the finger asset -- the product loads the same asset (model_root "synthetic:fingers") and the batch
-    comes from the interlocked generator."""
+    comes from the interlocked generator; overlap="deep": the deep-overlap batch."""
     from ihmr_amd.optimize_model import OptimizeModel
     from ihmr_amd.strategies import make_opt_strategy
     from oracle.opt_ref import OptimizeRef
     right, left = mano_arrays
-    _, batch = _two_hand_verts(mano_arrays, B, seed, interlock=fingers)
+    _, batch = _two_hand_verts(mano_arrays, B, seed, interlock=fingers, overlap=overlap)
     orc = OptimizeRef(right, left, B, make_opt_strategy(epoch), save_mid_freq=freq, record=record)
     model = OptimizeModel(_make_opt(B, epoch=epoch, save_mid_freq=freq, model_root="synthetic:fingers" if fingers else ""))
     return orc, model, batch
@@ -766,6 +820,47 @@ def test_opt_batch64_matches_oracle_on_the_finger_asset(finger_arrays):
     _batch64_trajectory(finger_arrays, fingers=True)
 
 
+def test_opt_batch64_matches_oracle_under_deep_overlap(mano_arrays):
+    """The same trajectory test on the deep-overlap batch (tests/test_collision_geometry_cpu.py: ~4 x the default batch's inside voxels
+    per hand, hands past the first ray-queue window), same keys and tolerances.  The selections must be the oracle's; a flip is only
+    accepted where the float64 arbiter explains it (the headline test's rule: at most 2 more disagreements with the float64 run than the
+    float32 oracle has), and the samples that flipped are left out of the element-wise comparison.  The batch must stay deep: its mean
+    penetration depth after the schedule is several times the default batch's under the same schedule."""
+    from helpers import DEEP_SEED
+    from ihmr_amd.optimize_model import OptimizeModel
+    B, epoch, freq = 64, 4, 2
+    orc, model, batch = _oracle_and_model(mano_arrays, B, epoch, freq, seed=DEEP_SEED, record=False, overlap="deep")
+    torch.set_num_threads(max(1, min(32, (__import__("os").cpu_count() or 8))))
+    orc.set_input(batch); orc.init_optimize(); orc.optimize()
+    model.set_input(batch); model.init_optimize(); model.optimize()
+    torch.cuda.synchronize()
+    r, g = orc.get_pred_result(), model.get_pred_result()
+    sel_ref, sel_got = np.stack(orc.selected), torch.stack(model.selected_history).cpu().numpy()
+    same = np.all(sel_ref == sel_got, axis=0)
+    print(f"[parity] deep B=64: selection agreement {float((sel_ref == sel_got).mean()):.4f} ({int((~same).sum())} samples differ)")
+    if not same.all():
+        _, sel_f64, _ = _f64_arbiter(mano_arrays, B, epoch, freq, batch)
+        print(f"[parity] deep B=64 arbiter: hip vs f64 differ at {int((sel_got != sel_f64).sum())}, oracle32 vs f64 at "
+              f"{int((sel_ref != sel_f64).sum())} of {sel_f64.size} (stage, sample) pairs")
+        assert (sel_got != sel_f64).sum() <= (sel_ref != sel_f64).sum() + 2
+    assert same.sum() >= B - 4
+    _report("deep B=64 pose", g["pred_pose_params"][same], r["pred_pose_params"][same], atol=2e-4)
+    _report("deep B=64 shape", g["pred_shape_params"][same], r["pred_shape_params"][same], atol=2e-4)
+    _report("deep B=64 trans", g["pred_hand_trans"][same], r["pred_hand_trans"][same], atol=2e-5)
+    _report("deep B=64 right verts [m]", g["pred_right_hand_verts"][same], r["pred_right_hand_verts"][same], atol=1e-4)
+    _report("deep B=64 left verts [m]", g["pred_left_hand_verts"][same], r["pred_left_hand_verts"][same], atol=1e-4)
+    _report("deep B=64 joints [m]", g["pred_joints_3d"][same], r["pred_joints_3d"][same], atol=1e-4)
+    _report("deep B=64 penetration depth [m]", g["collision_loss_origin_scale"][same], r["collision_loss_origin_scale"][same], atol=1e-4)
+    _report("deep B=64 collision_loss", g["collision_loss"][same], r["collision_loss"][same], atol=2e-4, rtol=1e-3)
+    _, shallow = _two_hand_verts(mano_arrays, B, 6464)            # (the default batch of test_opt_batch64_matches_oracle)
+    m2 = OptimizeModel(_make_opt(B, epoch=epoch, save_mid_freq=freq))
+    m2.set_input(shallow); m2.init_optimize(); m2.optimize()
+    torch.cuda.synchronize()
+    deep_pen, shallow_pen = float(r["collision_loss_origin_scale"].mean()), float(m2.get_pred_result()["collision_loss_origin_scale"].mean())
+    print(f"[parity] mean penetration depth after 4 x 5 iterations: deep batch {deep_pen:.3e} m, default batch {shallow_pen:.3e} m")
+    assert deep_pen >= 3 * shallow_pen          # (oracle: 1.0e-3 against 2.2e-4 m)
+
+
 def _batch64_trajectory(mano_arrays, fingers):
     B, epoch, freq = 64, 4, 2
     orc, model, batch = _oracle_and_model(mano_arrays, B, epoch, freq, seed=6464, record=False, fingers=fingers)
@@ -1038,16 +1133,19 @@ def test_sdf_convention_switches_match_oracle(mano_arrays, align_corners, loss_d
 
 
 # ----------------------------------------------------------------------------------- candidate lists are exact
-@pytest.mark.parametrize("B,epoch", [(16, 29), (64, 9)])
-def test_candidate_lists_do_not_change_a_bit(mano_arrays, B, epoch):
+@pytest.mark.parametrize("B,epoch,overlap", [pytest.param(16, 29, None, id="16-29"), pytest.param(64, 9, None, id="64-9"),
+                                             pytest.param(64, 14, "deep", id="deep-64-14"), pytest.param(160, 14, "deep", id="deep-160-14")])
+def test_candidate_lists_do_not_change_a_bit(mano_arrays, B, epoch, overlap):
     """Inside a stage the distance kernel searches, per voxel, only the candidate triangles recorded when the hand's lists were
     last built (valid while no vertex has moved by more than the slack in the hand's normalised frame; rebuilt otherwise, and at
     a stage start unless the caller vouches for its workspace: ihmr_opt_stage.keep_lists, round 6).  A conservative acceleration: with `opt.sdf_no_candidate_lists` every iteration searches all 1538
     triangles -- both runs must agree bit for bit, on the regular and on the ragged batch, through all four stages (the
-    translation / shape stages reuse the lists for many iterations, the orientation / pose stages rebuild every few)."""
-    from helpers import ragged_opt_batch
+    translation / shape stages reuse the lists for many iterations, the orientation / pose stages rebuild every few).  "deep": the
+    deep-overlap batch, where lists run long, are refused, and late voxels take fresh slots over 60-iteration stages; the snapshot
+    losses and the optimizer state are compared as well."""
+    from helpers import DEEP_SEED, ragged_opt_batch
     from ihmr_amd.optimize_model import OptimizeModel
-    _, batch = _two_hand_verts(mano_arrays, B, 900 + B)
+    _, batch = _two_hand_verts(mano_arrays, B, DEEP_SEED if overlap else 900 + B, overlap=overlap)
     if B == 16:
         batch = ragged_opt_batch(batch)
     outs = []
@@ -1058,28 +1156,31 @@ def test_candidate_lists_do_not_change_a_bit(mano_arrays, B, epoch):
         for rep in range(2):            # the second pass replays the captured graphs over the previous pass's (stale) lists
             m.set_input(batch); m.init_optimize(); m.optimize()
             torch.cuda.synchronize()
-        outs.append((m.get_pred_result(), torch.stack(m.selected_history).cpu().numpy()))
-    (a, sa), (b, sb) = outs
+        outs.append((m.get_pred_result(), torch.stack(m.selected_history).cpu().numpy(), m.buf["snap_loss"].cpu().numpy(), m.buf["adam_m"].cpu().numpy()))
+    (a, sa, la, ma), (b, sb, lb, mb) = outs
     assert np.array_equal(sa, sb)
+    if overlap:
+        assert np.array_equal(la, lb) and np.array_equal(ma, mb)
     for k in ("pred_pose_params", "pred_shape_params", "pred_hand_trans", "pred_right_hand_verts", "pred_left_hand_verts",
               "pred_joints_3d", "collision_loss", "collision_loss_origin_scale"):
         assert np.array_equal(a[k], b[k]), f"{k}: the candidate lists changed the result"
     assert float(a["collision_loss_origin_scale"].max()) > 0
 
 
-@pytest.mark.parametrize("B,epoch", [(16, 39), (64, 14)])
-def test_static_hand_reuse_does_not_change_a_bit(mano_arrays, B, epoch):
+@pytest.mark.parametrize("B,epoch,overlap", [pytest.param(16, 39, None, id="16-39"), pytest.param(64, 14, None, id="64-14"),
+                                             pytest.param(64, 14, "deep", id="deep-64-14"), pytest.param(160, 14, "deep", id="deep-160-14")])
+def test_static_hand_reuse_does_not_change_a_bit(mano_arrays, B, epoch, overlap):
     """A hand whose vertices cannot change during a stage keeps, from the stage's second iteration on, its box, normalised vertices
     and triangle records, and what earlier iterations found out about its voxels (inside / outside, distance): only voxels that the
     other hand reaches for the first time are tested and searched.  The same vertices give the same grid, so `opt.sdf_no_static_reuse`
     (everything from scratch every iteration) must agree bit for bit.  Stages: opt_default (translation stage: the right hands are
     static) + three that opt_default never runs -- right orientation alone (the left hands are static), left finger pose alone
     (the right hands are static while the other side rebuilds its candidate lists), camera + translation (right static, camera
-    gradient on) -- regular and ragged batch, graphs replayed twice over stale state."""
-    from helpers import ragged_opt_batch
+    gradient on) -- regular, ragged and deep-overlap batch, graphs replayed twice over stale state."""
+    from helpers import DEEP_SEED, ragged_opt_batch
     from ihmr_amd.optimize_model import OptimizeModel
     from ihmr_amd.strategies import make_opt_strategy
-    _, batch = _two_hand_verts(mano_arrays, B, 3100 + B)
+    _, batch = _two_hand_verts(mano_arrays, B, DEEP_SEED if overlap else 3100 + B, overlap=overlap)
     if B == 16:
         batch = ragged_opt_batch(batch)
     base = make_opt_strategy(epoch)
@@ -1106,19 +1207,24 @@ def test_static_hand_reuse_does_not_change_a_bit(mano_arrays, B, epoch):
     assert float(a["collision_loss_origin_scale"].max()) > 0
 
 
-@pytest.mark.parametrize("B,epoch,translated", [(16, 29, False), (64, 14, False), (160, 9, True)])
-def test_lists_kept_across_stage_boundaries_do_not_change_a_bit(mano_arrays, B, epoch, translated):
+@pytest.mark.parametrize("B,epoch,translated,overlap", [pytest.param(16, 29, False, None, id="16-29-False"),
+                                                       pytest.param(64, 14, False, None, id="64-14-False"),
+                                                       pytest.param(160, 9, True, None, id="160-9-True"),
+                                                       pytest.param(64, 14, False, "deep", id="deep-64-14-False"),
+                                                       pytest.param(160, 14, True, "deep", id="deep-160-14-True")])
+def test_lists_kept_across_stage_boundaries_do_not_change_a_bit(mano_arrays, B, epoch, translated, overlap):
     """Round 6: `OptimizeModel.run_stage` tells the library (`ihmr_opt_stage.keep_lists`) when the workspace still holds the candidate
     lists of the SAME batch's previous stage; the stage's first iteration then resets only the static-hand bookkeeping and a hand keeps its
     lists while the prep kernel's own displacement test passes -- whether an optimizer step or the previous stage's select step moved
     it.  An exact acceleration: `opt.sdf_no_stage_list_reuse` (every stage rebuilds, rounds 1-5) must agree bit for bit, over
     opt_default + three stages it never runs (so that every kind of stage follows every other kind), on the regular, the ragged and the
     >128-hand batch (the 512-thread form of the prep kernel), graphs replayed twice.  The flag is the caller's guarantee about its
-    workspace: set_input / init_optimize / a single-shot forward clear it, a fresh instance never sets it in its first stage."""
-    from helpers import ragged_opt_batch
+    workspace: set_input / init_optimize / a single-shot forward clear it, a fresh instance never sets it in its first stage.
+    "deep": the same on the deep-overlap batch."""
+    from helpers import DEEP_SEED, ragged_opt_batch
     from ihmr_amd.optimize_model import OptimizeModel
     from ihmr_amd.strategies import make_opt_strategy
-    _, batch = _two_hand_verts(mano_arrays, B, 4700 + B)
+    _, batch = _two_hand_verts(mano_arrays, B, DEEP_SEED if overlap else 4700 + B, overlap=overlap)
     if B == 16:
         batch = ragged_opt_batch(batch)
     base = make_opt_strategy(epoch)
@@ -1154,7 +1260,7 @@ def test_lists_kept_across_stage_boundaries_do_not_change_a_bit(mano_arrays, B, 
         assert np.array_equal(a[k], b[k]), f"{k}: keeping the lists across the stage boundary changed the result"
     assert float(a["collision_loss_origin_scale"].max()) > 0
     on, off = rebuilt
-    print(f"[stage lists] B={B}: voxels rebuilt {on['voxels_rebuilt']} (kept) vs {off['voxels_rebuilt']} (every stage rebuilds); "
+    print(f"[stage lists] {overlap or 'regular'} B={B}: lists refused {on['lists_refused']} (kept) vs {off['lists_refused']}; voxels rebuilt {on['voxels_rebuilt']} (kept) vs {off['voxels_rebuilt']} (every stage rebuilds); "
           f"full search {on['voxels_full_search']} vs {off['voxels_full_search']}; inside {on['inside_voxels']} vs {off['inside_voxels']}")
     assert on["inside_voxels"] == off["inside_voxels"]
     assert on["voxels_rebuilt"] < off["voxels_rebuilt"]
@@ -1210,11 +1316,11 @@ def _translated_reuse_diff(batch, B, epoch, strategy):
     return worst
 
 
-@pytest.mark.parametrize("asset", ["mitten", "fingers"])
+@pytest.mark.parametrize("asset", ["mitten", "fingers", "deep"])
 @pytest.mark.parametrize("B,epoch", [(16, 39), (64, 49)])
 def test_translated_hand_reuse_in_numbers(mano_arrays, finger_arrays, asset, B, epoch):
     """Round 6 (review item 5): numbers on the one default-on acceleration that is not exact.  Sixteen batches per asset (the blob and
-    the five-finger mesh with interlocked hands) and size (16 ragged, 64): the full schedule + a camera + translation stage with the kept
+    the five-finger mesh with interlocked hands; "deep": the blob on the deep-overlap batch, where the collision term dominates) and size (16 ragged, 64): the full schedule + a camera + translation stage with the kept
     grid (default) against `opt.sdf_no_translated_reuse`, counting
       * (stage, sample) pairs that select another snapshot,
       * stored snapshot losses that differ at all, and by how much (relative),
@@ -1239,7 +1345,7 @@ def test_translated_hand_reuse_in_numbers(mano_arrays, finger_arrays, asset, B, 
     flips = pairs = loss_diff = loss_n = vox_diff = vox_n = 0
     worst_ulp, worst, worst_abs = 0.0, 0.0, 0.0
     for seed in range(9000, 9016):
-        _, batch = _two_hand_verts(arrays, B, seed + B, interlock=asset == "fingers")
+        _, batch = _two_hand_verts(arrays, B, seed + B, interlock=asset == "fingers", overlap="deep" if asset == "deep" else None)
         if B == 16:
             batch = ragged_opt_batch(batch)
         res = []
@@ -1271,20 +1377,22 @@ def test_translated_hand_reuse_in_numbers(mano_arrays, finger_arrays, asset, B, 
     assert flips == 0 and vox_diff == 0 and worst <= 5e-6 and worst_abs <= 5e-6, (flips, vox_diff, worst, worst_abs, worst_ulp)
 
 
-@pytest.mark.parametrize("B,optimizer", [(16, "adam"), (64, "adam"), (9, "sgd")])
-def test_fused_tail_launch_does_not_change_a_bit(mano_arrays, B, optimizer):
+@pytest.mark.parametrize("B,optimizer,overlap", [pytest.param(16, "adam", None, id="16-adam"), pytest.param(64, "adam", None, id="64-adam"),
+                                                pytest.param(9, "sgd", None, id="9-sgd"), pytest.param(64, "adam", "deep", id="deep-64-adam"),
+                                                pytest.param(160, "adam", "deep", id="deep-160-adam")])
+def test_fused_tail_launch_does_not_change_a_bit(mano_arrays, B, optimizer, overlap):
     """The stages that do not move the finger pose run the tail of an iteration -- collision sampling + losses, the LBS backward of
     both hands, the optimizer step + the next skeletons -- as ONE launch per sample (`opt_tail_kernel`); `opt.no_fused_tail` runs
     the three launches it replaces.  The same device functions in the same order: bit for bit the same results, on the regular
-    and the ragged batch, with Adam and SGD, graphs replayed twice."""
-    from helpers import ragged_opt_batch
+    and the ragged batch, with Adam and SGD, graphs replayed twice; on the deep-overlap batch over 60-iteration stages."""
+    from helpers import DEEP_SEED, ragged_opt_batch
     from ihmr_amd.optimize_model import OptimizeModel
-    _, batch = _two_hand_verts(mano_arrays, B, 1700 + B)
+    _, batch = _two_hand_verts(mano_arrays, B, DEEP_SEED if overlap else 1700 + B, overlap=overlap)
     if B == 16:
         batch = ragged_opt_batch(batch)
     outs = []
     for off in (False, True):
-        opt = _make_opt(B, epoch=7, save_mid_freq=3)
+        opt = _make_opt(B, epoch=14 if overlap else 7, save_mid_freq=3)
         opt.no_fused_tail = off
         opt.optimizer = optimizer
         m = OptimizeModel(opt)
@@ -1393,3 +1501,61 @@ def test_candidate_lists_are_used_and_accounted_for(mano_arrays):
     assert evaluated["no_static_reuse"] == evaluated["no_lists"]
     assert evaluated["default"] < 0.75 * evaluated["no_static_reuse"], evaluated
     assert evaluated["translated"] < 0.5 * evaluated["default"], evaluated
+
+
+@pytest.mark.parametrize("B", [16, 64])
+def test_candidate_lists_exact_over_the_reference_schedule_under_deep_overlap(mano_arrays, B):
+    """The reference's default schedule (opt_default at epoch 300: 4 x 301 iterations, a snapshot every 10) on the deep-overlap batch,
+    candidate lists on and off (`opt.sdf_no_candidate_lists`): bit for bit the same selections, snapshot losses, optimizer state and
+    exports.  Long stages with deep overlap are where late voxels keep taking fresh list slots until a hand's SDF_LCAP_V = 1024 run out,
+    and where lists longer than SDF_LCAP_L = 192 triangles are refused and the voxel is searched in full from then on.  The counters do
+    not tell a refusal for want of slots from one for length, so slot exhaustion is exercised here but not separately shown.  Asserted:
+    lists were refused and voxels searched in full, and every inside voxel was answered exactly once; the refused lists per sample and
+    iteration and the full-search share are printed per stage, with the default batch's under the same schedule beside them."""
+    from helpers import DEEP_SEED
+    from ihmr_amd.optimize_model import OptimizeModel
+    epoch, freq = 300, 10
+    _, deep = _two_hand_verts(mano_arrays, B, DEEP_SEED, overlap="deep")
+    _, shallow = _two_hand_verts(mano_arrays, B, DEEP_SEED)
+    its = B * (epoch + 1)
+
+    def counted(batch, tag):
+        m = OptimizeModel(_make_opt(B, epoch=epoch, save_mid_freq=freq))
+        m.set_input(batch); m.init_optimize()
+        m.selected_history, per_stage = [], []
+        for st in m.strategy:                      # (OptimizeModel.optimize, with the counters read per stage)
+            m.sdf_counters_start()
+            m.run_stage(st)
+            per_stage.append(m.sdf_counters_stop())
+            m.selected_history.append(m.buf["selected"].clone())
+        m.forward_losses(m.default_loss_weights)
+        torch.cuda.synchronize()
+        for i, c in enumerate(per_stage):
+            print(f"[lists] {tag} B={B} stage {i}: lists refused {c['lists_refused']} ({c['lists_refused'] / its:.3f} per sample and iteration), "
+                  f"full-search share {c['voxels_full_search'] / max(c['inside_voxels'], 1):.4f}, inside voxels {c['inside_voxels'] / its:.1f} "
+                  f"per sample and iteration")
+        return m, per_stage
+
+    m_on, c_deep = counted(deep, "deep")
+    _, c_shallow = counted(shallow, "default")
+    tot = {k: sum(c[k] for c in c_deep) for k in c_deep[0]}
+    ref = {k: sum(c[k] for c in c_shallow) for k in c_shallow[0]}
+    print(f"[lists] B={B} whole schedule: refused lists per sample and iteration {tot['lists_refused'] / (4 * its):.3f} (default batch "
+          f"{ref['lists_refused'] / (4 * its):.3f}), full-search share {tot['voxels_full_search'] / tot['inside_voxels']:.4f} (default batch "
+          f"{ref['voxels_full_search'] / max(ref['inside_voxels'], 1):.4f})")
+    assert tot["lists_refused"] > 0 and tot["voxels_full_search"] > 0
+    for c in c_deep:
+        assert c["voxels_from_lists"] + c["voxels_full_search"] == c["inside_voxels"]
+    opt = _make_opt(B, epoch=epoch, save_mid_freq=freq)
+    opt.sdf_no_candidate_lists = True
+    m_off = OptimizeModel(opt)
+    m_off.set_input(deep); m_off.init_optimize(); m_off.optimize()
+    torch.cuda.synchronize()
+    a, b = m_on.get_pred_result(), m_off.get_pred_result()
+    assert np.array_equal(torch.stack(m_on.selected_history).cpu().numpy(), torch.stack(m_off.selected_history).cpu().numpy())
+    assert np.array_equal(m_on.buf["snap_loss"].cpu().numpy(), m_off.buf["snap_loss"].cpu().numpy())
+    assert np.array_equal(m_on.buf["adam_m"].cpu().numpy(), m_off.buf["adam_m"].cpu().numpy())
+    for k in ("pred_cam_params", "pred_pose_params", "pred_shape_params", "pred_hand_trans", "pred_right_hand_verts", "pred_left_hand_verts",
+              "pred_joints_3d", "collision_loss", "collision_loss_origin_scale"):
+        assert np.array_equal(a[k], b[k]), f"{k}: the candidate lists changed the result over the long schedule"
+    assert float(a["collision_loss_origin_scale"].max()) > 0
