@@ -988,11 +988,15 @@ extern "C" int ihmr_bn_train_forward(const float* z, long M, int C, const float*
     const int S = bn_chunks(M, &rows_per);
     float* part = (float*)workspace;
     const dim3 grid = bn_grid(C, S);
-    // one pass over z: sum z and sum (z - z0)^2 with row 0 as the pivot, then mean / variance / invstd
-    hipLaunchKernelGGL(bn_partial_kernel<3>, grid, dim3(256), 0, st, z, (const float*)nullptr, (int)M, C, C, C, rows_per,
+    // two passes over z: sum z -> mean (chunks added in double), then sum (z - mean)^2 -> biased variance / invstd / running statistics
+    hipLaunchKernelGGL(bn_partial_kernel<0>, grid, dim3(256), 0, st, z, (const float*)nullptr, (int)M, C, C, C, rows_per,
                        (const float*)nullptr, (const float*)nullptr, part, (const float*)nullptr);
-    hipLaunchKernelGGL(bn_finish_stats_kernel, dim3((C + 15) / 16), dim3(256), 0, st, (const float*)part, z, S, C, M, mean, var, invstd, eps, running_mean,
-                       running_var, momentum);
+    hipLaunchKernelGGL(bn_finish_kernel, dim3((C + 15) / 16), dim3(256), 0, st, (const float*)part, S, 1, C, 1.0 / (double)M, mean,
+                       (float*)nullptr, 0.f, (float*)nullptr);
+    hipLaunchKernelGGL(bn_partial_kernel<1>, grid, dim3(256), 0, st, z, (const float*)nullptr, (int)M, C, C, C, rows_per,
+                       (const float*)mean, (const float*)nullptr, part, (const float*)nullptr);
+    hipLaunchKernelGGL(bn_finish_stats_kernel, dim3((C + 15) / 16), dim3(256), 0, st, (const float*)part, S, C, M, (const float*)mean, var,
+                       invstd, eps, running_mean, running_var, momentum);
     hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)((M * (C / 4) + 255) / 256)), dim3(256), 0, st, z, (const float*)mean,
                        (const float*)invstd, gamma, beta, residual, y, M, C, relu);
     return (int)hipGetLastError();

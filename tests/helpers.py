@@ -204,3 +204,25 @@ def ray_queue_pairs(hv, faces_right, faces_left, needed):
         n = c[bb, k1 + 1, j1 + 1] - c[bb, k0, j1 + 1] - c[bb, k1 + 1, j0] + c[bb, k0, j0]
         P[:, h] = np.where(ok, n, 0).sum(axis=1)
     return P
+
+
+def synthetic_mlp_batch(mano_arrays, B, seed):
+    """A synthetic IHMR-MLP batch with image features (``synthetic_opt_batch(..., with_feat=True)`` on the oracle's two-hand MANO),
+    in the layout MLPModel / MLPRef take: ``init_hand_trans`` (B,3), an 8 x 8 dummy image, no ``init_hand_trans_j``."""
+    from ihmr_amd.synthetic import synthetic_opt_batch
+    from oracle.opt_ref import OptimizeRef
+    right, left = mano_arrays
+    helper = OptimizeRef(right, left, B, [], save_mid_freq=1)
+
+    def fwd(pose, shape, trans):
+        helper.pred_right_orient, helper.pred_left_orient = pose[:, :3], pose[:, 48:51]
+        helper.pred_right_pose_params, helper.pred_left_pose_params = pose[:, 3:48], pose[:, 51:]
+        helper.pred_right_shape_params, helper.pred_left_shape_params = shape[:, :10], shape[:, 10:]
+        helper.pred_hand_trans = trans.view(-1, 1, 3)
+        return helper.get_mano_output()[2]
+
+    batch = synthetic_opt_batch(B, fwd, seed=seed, with_feat=True)
+    batch["init_hand_trans"] = batch["init_hand_trans"][:, 0, :3].contiguous()
+    batch["img"] = torch.zeros(B, 3, 8, 8)
+    batch.pop("init_hand_trans_j")
+    return batch

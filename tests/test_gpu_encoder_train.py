@@ -59,6 +59,139 @@ def test_batchnorm_train_forward_backward(N, C, H, W, res, relu):
     _close("bn dbeta", dbeta, beta.grad, 2e-5)
 
 
+def _bn_rows_per_chunk(M):
+    """bn_chunks() of ihmr_hip.hip: rows per chunk of the BatchNorm column reductions (BN_MAX_CHUNKS = 1024, at least 16)."""
+    return max(16, -(-M // 1024))
+
+
+def _vs_float64(name, hip_err, t32_err, floor):
+    """The whole-encoder rule: the HIP result is no further from float64 than 3 x torch-fp32's own distance, + `floor`."""
+    print(f"[parity] {name}: HIP vs float64 {hip_err:.3e}, torch-fp32 vs float64 {t32_err:.3e}, bar {3 * t32_err + floor:.3e}")
+    assert hip_err <= 3.0 * t32_err + floor, f"{name}: HIP {hip_err:.3e} vs torch-fp32 {t32_err:.3e} (+ floor {floor:.1e})"
+
+
+def _conv_output_with_offsets(N, Cimg, H, C, k, stride, pad, seed):
+    """z [N*Ho*Wo, C] = a real convolution (ihmr_conv_igemm) of an image-like input (smooth positive field + pixel noise, NHWC),
+    whose last input channel is constant 1: through zero padding, its weights give output channel c the offset off_c x (the
+    fraction of the pixel's taps that fall inside the image).  Row 0 is image 0's corner pixel, with 16 / 49 (7 x 7 stem)
+    or 4 / 9 (3 x 3) of its taps inside, so for a channel with a large offset the one-pass pivot z0 sits far from the mean.
+    Odd channels take their offset that way; even channels get a uniform offset on top (mean / std from 1 up to 100); channel 5's
+    row 0 is set to a 50 sigma outlier."""
+    from ihmr_amd import encoder_train as T
+    g = torch.Generator().manual_seed(seed)
+    Cin = Cimg + 1
+    img = F.interpolate(torch.rand(N, Cimg, max(H // 8, 2), max(H // 8, 2), generator=g), size=(H, H), mode="bilinear", align_corners=False)
+    img = img + 0.1 * torch.rand(N, Cimg, H, H, generator=g)
+    x = torch.cat([img, torch.ones(N, 1, H, H)], 1).permute(0, 2, 3, 1).reshape(-1, Cin).contiguous().cuda()
+    w = torch.randn(C, Cin, k, k, generator=g) / np.sqrt(Cimg * k * k)
+    w[:, -1] = 0.0
+    base, Ho, Wo = T.conv_forward(x, T.pack_forward_weight(w).cuda(), N, H, H, Cin, C, k, stride, pad)
+    sigma = base.double().std(0).cpu()
+    ratio = torch.logspace(0, 2, C // 2, dtype=torch.float64).repeat_interleave(2)      # target mean / std of channels 2j, 2j + 1
+    off = ratio * sigma
+    w[1::2, -1] = (off[1::2] / (k * k)).float()[:, None, None]
+    z, _, _ = T.conv_forward(x, T.pack_forward_weight(w).cuda(), N, H, H, Cin, C, k, stride, pad)
+    u = off.clone()
+    u[1::2] = 0.0
+    z += u.float().cuda()
+    z[0, 5] = float(z[:, 5].double().mean() + 50 * z[:, 5].double().std())
+    torch.cuda.synchronize()
+    return z, Ho, Wo
+
+
+@pytest.mark.parametrize("N,Cimg,H,C,k,stride,pad", [(64, 3, 224, 64, 7, 2, 3),       # the stem: 802 816 rows
+                                                       (64, 15, 56, 256, 3, 1, 1),      # layer 1 at batch 64
+                                                       (64, 15, 7, 2048, 3, 1, 1)])     # layer 4 at batch 64
+@pytest.mark.parametrize("res,relu", [(True, True), (False, False)])
+def test_batchnorm_at_training_shapes_vs_float64(N, Cimg, H, C, k, stride, pad, res, relu):
+    """ihmr_bn_train_forward / _backward at IHMR-Baseline's batch-64 shapes against float64 (the same formulas, evaluated in
+    float64 on the GPU), with torch-fp32 (F.batch_norm + autograd on the CPU) as the yardstick of what fp32 can do.  The
+    input is a convolution's output with large per-channel offsets and a 50 sigma outlier in row 0: the pivot of the
+    kernel's variance (row 0 of the matrix) is atypical, and a pivot-based one-pass variance loses 1 + (mean - z0)^2 / var of
+    its precision, a long fp32 chain per chunk adds to it."""
+    from ihmr_amd import encoder_train as T
+    z, Ho, Wo = _conv_output_with_offsets(N, Cimg, H, C, k, stride, pad, seed=C + H)
+    M = z.shape[0]
+    rows_per = _bn_rows_per_chunk(M)
+    chunks = -(-M // rows_per)
+    if C > 1024:    # the path: two column blocks over more chunks than the finish kernels' eight-chunk loop needs (earlier: 7)
+        assert C // 4 > 256 and chunks > 8 * 16, chunks
+    else:           # the path: more rows per chunk (one fp32 chain per thread and chunk) than any earlier BN test had (25)
+        assert rows_per > 25, rows_per
+    if k == 7:
+        assert M == N * Ho * Wo == 802816 and rows_per == 784
+    z64 = z.double()
+    mean64 = z64.mean(0)
+    var64 = (z64 - mean64).square().mean(0)
+    sd64 = var64.sqrt()
+    amp = ((mean64 - z64[0]).square() / var64)                  # the one-pass pivot's loss factor - 1
+    print(f"[parity] bn M={M} C={C}: rows per chunk {rows_per}, max mean/std {float((mean64.abs() / sd64).max()):.1f}, "
+          f"max (mean - z0)^2 / var {float(amp.max()):.0f}, median {float(amp.median()):.2f}")
+    assert float((mean64.abs() / sd64).max()) > 90 and float(amp.max()) > 1000
+    g = torch.Generator().manual_seed(C)
+    gamma = (torch.rand(C, generator=g) + 0.5)
+    beta = torch.randn(C, generator=g) * 0.2
+    r = (torch.randn(M, C, generator=g) if res else None)
+    dy = torch.randn(M, C, generator=g)
+    run = (torch.zeros(C, device="cuda"), torch.ones(C, device="cuda"))
+    y, (mean, var, invstd) = T.bn_train_forward(z, gamma.cuda(), beta.cuda(), r.cuda() if res else None, relu, running=run)
+    torch.cuda.synchronize()
+    # the backward of all three sides gets the same masked gradient (the mask of the HIP output: a pre-activation within rounding
+    # of zero must not decide the comparison); the HIP kernels apply that mask themselves (relu_y)
+    gm = dy.cuda() * (y > 0) if relu else dy.cuda()
+    dz, dgamma, dbeta = T.bn_train_backward(z, dy.cuda() if relu else gm, (mean, var, invstd), gamma.cuda(), relu_y=y if relu else None)
+    torch.cuda.synchronize()
+
+    # float64, on the GPU
+    invstd64 = 1.0 / (var64 + 1e-5).sqrt()
+    xhat64 = (z64 - mean64) * invstd64
+    y64 = xhat64 * gamma.double().cuda() + beta.double().cuda()
+    if res:
+        y64 = y64 + r.double().cuda()
+    if relu:
+        y64 = y64.clamp_min(0)
+    gm64 = gm.double()
+    dbeta64, dgamma64 = gm64.sum(0), (gm64 * xhat64).sum(0)
+    dz64 = gamma.double().cuda() * invstd64 * (gm64 - dbeta64 / M - xhat64 * (dgamma64 / M))
+
+    # torch fp32 on the CPU (F.batch_norm + autograd, channels-last views of the same matrices)
+    nchw = lambda t: t.reshape(N, Ho, Wo, C).permute(0, 3, 1, 2)
+    zc = nchw(z.cpu()).requires_grad_(True)
+    gc, bc = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+    rm32, rv32 = torch.zeros(C), torch.ones(C)
+    threads = torch.get_num_threads()
+    torch.set_num_threads(16)
+    try:
+        y32 = F.batch_norm(zc, rm32, rv32, gc, bc, training=True, momentum=0.1, eps=1e-5)
+        y32.backward(nchw(gm.cpu()))
+    finally:
+        torch.set_num_threads(threads)
+    y32 = y32.detach()
+    if res:
+        y32 = y32 + nchw(r)
+    if relu:
+        y32 = y32.clamp_min(0)
+    mean32 = zc.detach().mean(dim=(0, 2, 3))
+    var32 = zc.detach().var(dim=(0, 2, 3), unbiased=False)
+
+    def rel(a, b, s):                                            # max over channels of |a - b| / s
+        return float(((a.double().cpu() - b.double().cpu()).abs() / s.double().cpu()).max())
+    def tmax(a, b):
+        return float((a.double().cpu() - b.double().cpu()).abs().max())
+    ym = float(y64.abs().max())
+    _vs_float64("bn y (max |err|)", tmax(nchw(y.double().cpu()), nchw(y64.cpu())), tmax(y32, nchw(y64.cpu())), 1e-6 * ym)
+    _vs_float64("bn batch mean (|err| / std)", rel(mean, mean64, sd64), rel(mean32, mean64, sd64), 2e-7)
+    _vs_float64("bn batch var (relative)", rel(var, var64, var64), rel(var32, var64, var64), 5e-7)
+    _vs_float64("bn invstd (relative)", rel(invstd, invstd64, invstd64), rel(1.0 / (var32.double() + 1e-5).sqrt(), invstd64, invstd64), 5e-7)
+    _vs_float64("bn running_mean (|err| / std)", rel(run[0], 0.1 * mean64, sd64), rel(rm32, 0.1 * mean64, sd64), 2e-7)
+    rv64 = 0.9 + 0.1 * var64 * M / (M - 1)
+    _vs_float64("bn running_var (relative)", rel(run[1], rv64, rv64), rel(rv32, rv64, rv64), 5e-7)
+    dzm = float(dz64.abs().max())
+    _vs_float64("bn dz (max |err|)", tmax(nchw(dz.cpu()), nchw(dz64.cpu())), tmax(zc.grad, nchw(dz64.cpu())), 1e-6 * dzm)
+    _vs_float64("bn dgamma (max |err|)", tmax(dgamma, dgamma64), tmax(gc.grad, dgamma64), 1e-6 * float(dgamma64.abs().max()))
+    _vs_float64("bn dbeta (max |err|)", tmax(dbeta, dbeta64), tmax(bc.grad, dbeta64), 1e-6 * float(dbeta64.abs().max()))
+
+
 CONVS = [  # N, Cin, H, W, Cout, k, stride, pad
     (4, 64, 16, 16, 64, 1, 1, 0), (2, 64, 14, 14, 64, 3, 1, 1), (2, 128, 16, 16, 128, 3, 2, 1), (2, 256, 8, 8, 512, 1, 2, 0),
     (2, 4, 32, 32, 64, 7, 2, 3), (3, 512, 7, 7, 2048, 1, 1, 0), (2, 512, 7, 7, 512, 3, 1, 1), (8, 64, 56, 56, 256, 1, 1, 0),

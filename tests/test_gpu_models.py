@@ -161,27 +161,13 @@ def test_mlp_model_batch128_matches_oracle(mano_arrays):
     """BASELINE.json's IHMR-MLP configuration (batch 128 = 256 hands through the fused forward / collision launches, the
     Linear layers at M = 128): all six stages of MLPModel.test() against the oracle's MLPRef.test() -- per-stage
     keep / reject decisions identical, parameters, meshes and penetration depths within the bars."""
-    from helpers import seeded_state_dict
+    from helpers import seeded_state_dict, synthetic_mlp_batch
     from ihmr_amd.mlp_model import MLPModel
     from ihmr_amd.strategies import make_mlp_strategy
-    from ihmr_amd.synthetic import synthetic_opt_batch
     from oracle.mlp_ref import MLPRef
-    from oracle.opt_ref import OptimizeRef
     right, left = mano_arrays
     B = 128
-    helper = OptimizeRef(right, left, B, [], save_mid_freq=1)
-
-    def fwd(pose, shape, trans):
-        helper.pred_right_orient, helper.pred_left_orient = pose[:, :3], pose[:, 48:51]
-        helper.pred_right_pose_params, helper.pred_left_pose_params = pose[:, 3:48], pose[:, 51:]
-        helper.pred_right_shape_params, helper.pred_left_shape_params = shape[:, :10], shape[:, 10:]
-        helper.pred_hand_trans = trans.view(-1, 1, 3)
-        return helper.get_mano_output()[2]
-
-    batch = synthetic_opt_batch(B, fwd, seed=128128, with_feat=True)
-    batch["init_hand_trans"] = batch["init_hand_trans"][:, 0, :3].contiguous()
-    batch["img"] = torch.zeros(B, 3, 8, 8)
-    batch.pop("init_hand_trans_j")
+    batch = synthetic_mlp_batch(mano_arrays, B, seed=128128)
     batch["joints_3d"][5, 0, 3] = 0.0
     batch["hand_type_array"][7] = torch.tensor([1.0, 0.0])
     strategy = make_mlp_strategy()
@@ -230,30 +216,13 @@ def test_mlp_camera_stage_shortcut_does_not_change_a_bit(mano_arrays):
     (`ihmr_mlp_forward_select` mode 3; `opt.mlp_no_vposed_reuse` = both blends every time).  Bit for bit the same decisions, "prev" tables and exports, over two test() calls
     (the second compares against the tables the first one left) on a batch with both decisions in the camera stage -- and a
     strategy whose FIRST stage is the camera one (the accepted joints are then the first evaluation's)."""
-    from helpers import seeded_state_dict
+    from helpers import seeded_state_dict, synthetic_mlp_batch
     from ihmr_amd.mlp_model import MLPModel
     from ihmr_amd.strategies import make_mlp_strategy
-    from ihmr_amd.synthetic import synthetic_opt_batch
     from oracle.mlp_ref import MLPRef
-    from oracle.opt_ref import OptimizeRef
     right, left = mano_arrays
     B = 32
-    helper = OptimizeRef(right, left, B, [], save_mid_freq=1)
-
-    def fwd(pose, shape, trans):
-        helper.pred_right_orient, helper.pred_left_orient = pose[:, :3], pose[:, 48:51]
-        helper.pred_right_pose_params, helper.pred_left_pose_params = pose[:, 3:48], pose[:, 51:]
-        helper.pred_right_shape_params, helper.pred_left_shape_params = shape[:, :10], shape[:, 10:]
-        helper.pred_hand_trans = trans.view(-1, 1, 3)
-        return helper.get_mano_output()[2]
-
-    batches = []
-    for seed in (3232, 3233):
-        b = synthetic_opt_batch(B, fwd, seed=seed, with_feat=True)
-        b["init_hand_trans"] = b["init_hand_trans"][:, 0, :3].contiguous()
-        b["img"] = torch.zeros(B, 3, 8, 8)
-        b.pop("init_hand_trans_j")
-        batches.append(b)
+    batches = [synthetic_mlp_batch(mano_arrays, B, seed=seed) for seed in (3232, 3233)]
     base = make_mlp_strategy()
     for strategy in (base, [base[5]] + base[:5]):
         orc = MLPRef(right, left, B, strategy, num_data=B)
