@@ -40,6 +40,10 @@ class InterHandModel(BaselineTrainMixin):
         hip.require_gpu()
         self.opt = opt
         self.isTrain = getattr(opt, "isTrain", False)
+        # opt.encoder_precision: "fp32" (default) | "bf16" -- the ResNet-50 trunk on the bf16 matrix cores (networks.InterHandEncoder);
+        # inference only: the training step differentiates the fp32 kernels
+        if self.isTrain and getattr(opt, "encoder_precision", "fp32") != "fp32":
+            raise ValueError("encoder_precision = %r is an inference option; training runs in fp32 (isTrain = True)" % (opt.encoder_precision,))
         self.inputSize = opt.inputSize
         self.batch_size = opt.batchSize
         self.cam_params_dim, self.pose_params_dim = opt.cam_params_dim, opt.pose_params_dim

@@ -8,7 +8,8 @@
 //
 // GEMM view: Y[M = N*Ho*Wo][Cout] = A[M][K = kh*kw*Cin] . Wt[K][Cout], A gathered on the fly (never stored).
 // MFMA: v_mfma_f32_32x32x2_f32 -- f32 in / f32 accumulate, bit-for-bit a k-ordered fmaf chain, 157 TFLOP/s
-// peak on MI355X; the reference is fp32 end to end, so no reduced-precision path is needed for parity.
+// peak on MI355X; the reference is fp32 end to end, so this fp32 path is the default and the one every parity claim rests on.
+// An opt-in bf16 form of the trunk (encoder_precision = "bf16": bf16 operands, fp32 accumulation) lives in encoder_bf16.h.
 // Tile: BM x BN x 16 per workgroup (BM = 64 | 128, BN = 64 | 128), one wave per 64 x 32 sub-tile (2 to 8 waves);
 // A is staged K-major in LDS so that the 32 lanes of an MFMA row read consecutive addresses; LDS is
 // double-buffered: the global loads of tile t+1 are issued before the MFMAs of tile t and stored to the other

@@ -16,6 +16,7 @@
 #include "mlp_infer.h"
 #include "refine.h"
 #include "encoder.h"
+#include "encoder_bf16.h"
 #include "evaluate.h"
 #include "train.h"
 #include "train_conv.h"
@@ -896,6 +897,77 @@ extern "C" int ihmr_avgpool_relu(const float* x, float* y, int N, int HW, int C,
     return (int)hipGetLastError();
 }
 
+// ---- bf16 encoder path (csrc/encoder_bf16.h)
+extern "C" int ihmr_conv_igemm_bf16(const uint16_t* x, const uint16_t* w, const float* bias, const uint16_t* residual, uint16_t* y, int N,
+                                    int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int ldx,
+                                    int ldw, int ldy, int ldr, int act, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x || !w || !y || N <= 0 || Cout <= 0 || Cin <= 0 || (act != 0 && act != 1) || ldw % 64 != 0 || ldw < Cout) return -1;
+    if (((uintptr_t)w % 16) != 0 || (bias && ((uintptr_t)bias % 16) != 0)) return -1;
+    const int M = N * Ho * Wo, nk = (kh * kw * Cin + CONVB_BK - 1) / CONVB_BK;
+    hipStream_t st = (hipStream_t)stream;
+    const bool wide = Cout > 64 && ldw % 128 == 0;
+    const int BN = wide ? 128 : 64;
+    if (ldw < (Cout + BN - 1) / BN * BN) return -1;
+    const int vec = Cout % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)y % 8) == 0 && (!residual || (ldr % 4 == 0 && ((uintptr_t)residual % 8) == 0));
+    ConvArgsBF16 a{x, w, bias, residual, y, N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, ldx, ldw, ldy, ldr, act, (float*)workspace, 1, vec};
+    // K split: a layer with fewer than two tiles per CU (at batch 64: the 14 x 14 and 7 x 7 stages) runs its K loop in up to 8 pieces of
+    // at least 4 steps; the pieces' fp32 sums go to the workspace and are added in ascending K order (bit-identical from run to run;
+    // the split follows the device's CU count, so results are bit-stable per device model)
+    int cus = 0;
+    if (int rc = device_cu_count(&cus)) return rc;
+    const long tiles = (long)((M + 127) / 128) * ((Cout + BN - 1) / BN);
+    int ksplit = 1;
+    if (workspace && tiles < 2L * cus && nk >= 8) {
+        const long cap = (long)(workspace_bytes / ((size_t)M * Cout * sizeof(float)));
+        ksplit = (int)std::max<long>(1, std::min<long>(std::min<long>(8, cap), std::min<long>(nk / 4, (2L * cus + tiles - 1) / tiles)));
+    }
+    a.ksplit = ksplit;
+    const dim3 grid((M + 127) / 128, (Cout + BN - 1) / BN, ksplit), block(256);
+    const int mode = (Cin % CONVB_BK == 0 && ldx % 8 == 0 && Cin <= 4096 && ((uintptr_t)x % 16) == 0) ? CONVB_FAST
+                   : (Cin == 4 && ldx == 4 && ((uintptr_t)x % 8) == 0) ? CONVB_C4 : CONVB_GENERIC;
+    if (wide) {
+        if (mode == CONVB_FAST) hipLaunchKernelGGL((conv_igemm_bf16_kernel<128, CONVB_FAST>), grid, block, 0, st, a);
+        else if (mode == CONVB_C4) hipLaunchKernelGGL((conv_igemm_bf16_kernel<128, CONVB_C4>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((conv_igemm_bf16_kernel<128, CONVB_GENERIC>), grid, block, 0, st, a);
+    } else {
+        if (mode == CONVB_FAST) hipLaunchKernelGGL((conv_igemm_bf16_kernel<64, CONVB_FAST>), grid, block, 0, st, a);
+        else if (mode == CONVB_C4) hipLaunchKernelGGL((conv_igemm_bf16_kernel<64, CONVB_C4>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((conv_igemm_bf16_kernel<64, CONVB_GENERIC>), grid, block, 0, st, a);
+    }
+    if (ksplit > 1) {
+        const long total = (long)M * ((Cout + 3) / 4);
+        hipLaunchKernelGGL(conv_splitk_reduce_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int ihmr_pack_image_bf16(const float* img, uint16_t* y, int N, int H, int W, void* stream) {
+    if (!img || !y || N <= 0 || H <= 0 || W <= 0 || ((uintptr_t)y % 8) != 0) return -1;
+    const long total = (long)N * H * W;
+    hipLaunchKernelGGL(image_to_nhwc4_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, img, y, N, H * W);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ihmr_maxpool3x3s2_bf16(const uint16_t* x, uint16_t* y, int N, int H, int W, int C, int Ho, int Wo, void* stream) {
+    if (!x || !y || C % 8 || ((uintptr_t)x % 16) != 0 || ((uintptr_t)y % 16) != 0) return -1;
+    const long total = (long)N * Ho * Wo * (C / 8);
+    hipLaunchKernelGGL(maxpool3x3s2_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, N, H, W, C, Ho, Wo);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ihmr_avgpool_relu_bf16(const uint16_t* x, float* y, int N, int HW, int C, int ldy, void* stream) {
+    if (!x || !y || C % 8 || ((uintptr_t)x % 16) != 0) return -1;
+    hipLaunchKernelGGL(avgpool_relu_bf16_kernel, dim3((N * (C / 8) + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, y, N, HW, C, ldy);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ihmr_cast_f32_bf16(const float* x, uint16_t* y, size_t n, void* stream) {
+    if (!x || !y) return -1;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, n);
+    return (int)hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------ misc
 // ------------------------------------------------------------------------------------------ evaluator
 extern "C" int ihmr_eval_metrics(const float* pred_joints_3d, const float* gt_joints_3d, const float* coll_origin_scale,
@@ -1265,4 +1337,4 @@ extern "C" long ihmr_debug_timeline(unsigned long long* host, long cap) {
 }
 #endif
 
-extern "C" const char* ihmr_version(void) { return "ihmr_hip 0.1 (gfx950)"; }
+extern "C" const char* ihmr_version(void) { return "ihmr_hip 0.2 (gfx950)"; }

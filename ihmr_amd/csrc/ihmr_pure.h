@@ -282,3 +282,21 @@ IHMR_PURE float opt_sgd_update(float x, float g, float& m, float lr) {
     m = m + g;
     return x + (-lr) * m;
 }
+
+// ------------------------------------------------------------------------------------- bf16 encoder path (csrc/encoder_bf16.h)
+// fp32 -> bf16, round to nearest even on the bit pattern -- the bits of torch's `tensor.bfloat16()`: ties go to the even neighbour,
+// a value above the largest finite bf16 rounds to +-inf, +-inf and +-0 keep their bits, every NaN becomes the quiet NaN 0x7FC0.
+IHMR_PURE uint16_t ihmr_f32_to_bf16(float f) {
+    uint32_t u;
+    __builtin_memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)0x7fc0;
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+// bf16 -> fp32 (exact)
+IHMR_PURE float ihmr_bf16_to_f32(uint16_t v) {
+    const uint32_t u = (uint32_t)v << 16;
+    float f;
+    __builtin_memcpy(&f, &u, 4);
+    return f;
+}

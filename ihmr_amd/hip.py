@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = [
     "ihmr_dilate2", "ihmr_interleave2", "ihmr_pack_dgrad_weight", "ihmr_maxpool3x3s2_backward", "ihmr_avgpool_relu_backward", "ihmr_set_kernel_timer", "ihmr_flush_kernel_timer",
     "ihmr_mlp_workspace_bytes", "ihmr_mlp_stage_head", "ihmr_mlp_forward_select", "ihmr_mlp_camera_select", "ihmr_opt_forward_verts",
     "ihmr_debug_force_lbs_bwd2_streaming", "ihmr_debug_force_full_skin", "ihmr_version", "ihmr_copy_segments", "ihmr_root_align_joints",
+    "ihmr_conv_igemm_bf16", "ihmr_pack_image_bf16", "ihmr_maxpool3x3s2_bf16", "ihmr_avgpool_relu_bf16", "ihmr_cast_f32_bf16",
 ]
 
 
@@ -275,6 +276,11 @@ def lib():
         L.ihmr_conv_igemm.argtypes = [vp, vp, vp, vp, vp] + [i] * 16 + [vp, C.c_size_t, vp]
         L.ihmr_maxpool3x3s2.argtypes = [vp, vp, i, i, i, i, i, i, vp]
         L.ihmr_avgpool_relu.argtypes = [vp, vp, i, i, i, i, vp]
+        L.ihmr_conv_igemm_bf16.argtypes = [vp, vp, vp, vp, vp] + [i] * 16 + [vp, C.c_size_t, vp]
+        L.ihmr_pack_image_bf16.argtypes = [vp, vp, i, i, i, vp]
+        L.ihmr_maxpool3x3s2_bf16.argtypes = [vp, vp, i, i, i, i, i, i, vp]
+        L.ihmr_avgpool_relu_bf16.argtypes = [vp, vp, i, i, i, i, vp]
+        L.ihmr_cast_f32_bf16.argtypes = [vp, vp, C.c_size_t, vp]
         L.ihmr_mlp_train_grad.argtypes = [vp, vp, C.POINTER(OptIO), i, C.POINTER(OptWeights), C.POINTER(TrainWeights)] + [vp] * 8 + [i, vp, i, vp]
         L.ihmr_transpose.argtypes = [vp, vp, i, i, i, i, vp]
         L.ihmr_relu_backward.argtypes = [vp, vp, i, i, i, i, vp]

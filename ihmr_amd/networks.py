@@ -7,6 +7,8 @@ reference's keys (``main_encoder.conv1.weight`` ... ``regressor_ih.0.bias``) and
 with ``load_state_dict`` unchanged (``base_model.py:45-61``).  Their ``forward`` is never called: every
 convolution / linear layer runs as an fp32 implicit GEMM on the matrix cores (``ihmr_conv_igemm``), with
 BatchNorm (eval mode) folded into the packed weights and ReLU / residual / sigmoid fused into the epilogue.
+``opt.encoder_precision = "bf16"`` (inference only, opt-in) runs the ResNet-50 trunk on the bf16 matrix cores instead
+(``ihmr_conv_igemm_bf16``: bf16 activations and weights, fp32 accumulation and epilogue); the heads stay fp32.
 The reference forces ``pretrained=True`` (a URL download, ``networks.py:40``); here weights come from
 ``load_state_dict`` or stay at their random initialisation.
 """
@@ -43,6 +45,34 @@ class _Packed:
         self.cout, self.cin, self.kh, self.kw, self.stride, self.pad, self.ldw = cout, cin + k_extra, kh, kw, stride, pad, ldw
 
 
+class _PackedBF16:
+    """Device-resident bf16 weight of one trunk conv in the order ``conv_igemm_bf16_kernel`` reads it: ``[Kpad / 8][ldw][8]``, i.e.
+    element (k, n) of the K-major ``[K][Cout]`` matrix at ``((k // 8) * ldw + n) * 8 + k % 8`` (a lane's operand fragment -- 8
+    consecutive k of one output channel -- is one 16-byte load), Kpad = ceil32(K), zero padded.  ``weight4d`` / ``bias`` are the
+    BN-folded fp32 tensors (``_fold_bn``); the weight is rounded to bf16 here (round-to-nearest-even), the bias stays fp32."""
+
+    def __init__(self, weight4d: torch.Tensor, bias: torch.Tensor, stride=1, pad=0, k_extra=0):
+        cout, cin, kh, kw = weight4d.shape
+        K = kh * kw * (cin + k_extra)
+        wk = weight4d.permute(2, 3, 1, 0)                                  # [kh][kw][cin][cout]
+        if k_extra:
+            wk = torch.cat([wk, wk.new_zeros(kh, kw, k_extra, cout)], dim=2)
+        wk = wk.reshape(K, cout).bfloat16()
+        ldw = _ceil(cout, 128) if cout > 64 else 64
+        kpad = _ceil(K, 32)
+        full = wk.new_zeros(kpad, ldw)
+        full[:K, :cout] = wk
+        self.w = full.view(kpad // 8, 8, ldw).permute(0, 2, 1).contiguous()   # [Kpad / 8][ldw][8]
+        self.b = bias.float().contiguous()
+        self.K, self.kpad = K, kpad
+        self.cout, self.cin, self.kh, self.kw, self.stride, self.pad, self.ldw = cout, cin + k_extra, kh, kw, stride, pad, ldw
+
+    def unpack(self, padded=False):
+        """The K-major bf16 matrix back: ``[K][Cout]`` (or the whole ``[Kpad][ldw]`` with its zero padding)."""
+        full = self.w.permute(0, 2, 1).reshape(self.kpad, self.ldw)
+        return full if padded else full[:self.K, :self.cout]
+
+
 def _fold_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d):
     scale = bn.weight.detach() / torch.sqrt(bn.running_var.detach() + bn.eps)
     return conv.weight.detach() * scale[:, None, None, None], bn.bias.detach() - bn.running_mean.detach() * scale
@@ -74,6 +104,24 @@ def conv_igemm(x, pk: _Packed, N, H, W, ldx, out=None, ldy=None, residual=None, 
                                         out.data_ptr(), N, H, W, pk.cin, Ho, Wo, pk.cout, pk.kh, pk.kw, pk.stride, pk.pad,
                                         ldx, pk.ldw, ldy, ldr, act, ws.data_ptr(), ws.numel() * 4, hip.stream_ptr()), "ihmr_conv_igemm")
     return out, Ho, Wo
+
+
+def conv_igemm_bf16(x, pk: _PackedBF16, N, H, W, ldx, out=None, ldy=None, residual=None, ldr=0, act=0):
+    """x: device bf16 tensor holding NHWC activations (pixel stride ldx).  Returns (y bf16, Ho, Wo)."""
+    Ho = (H + 2 * pk.pad - pk.kh) // pk.stride + 1
+    Wo = (W + 2 * pk.pad - pk.kw) // pk.stride + 1
+    assert x.dtype == torch.bfloat16 and (residual is None or residual.dtype == torch.bfloat16)
+    if out is None:
+        out = torch.empty(N * Ho * Wo, pk.cout, device=x.device, dtype=torch.bfloat16)
+        ldy = pk.cout
+    ws = _splitk_workspace(x.device)
+    hip.check(hip.lib().ihmr_conv_igemm_bf16(hip.ptr(x), hip.ptr(pk.w), hip.ptr(pk.b), None if residual is None else residual.data_ptr(),
+                                             out.data_ptr(), N, H, W, pk.cin, Ho, Wo, pk.cout, pk.kh, pk.kw, pk.stride, pk.pad,
+                                             ldx, pk.ldw, ldy, ldr, act, ws.data_ptr(), ws.numel() * 4, hip.stream_ptr()), "ihmr_conv_igemm_bf16")
+    return out, Ho, Wo
+
+
+ENCODER_PRECISIONS = ("fp32", "bf16")
 
 
 class _Bottleneck(nn.Module):  # parameter container, resnet.py:58-94
@@ -118,12 +166,76 @@ class InterHandEncoder(nn.Module):
         self.feat_encoder = nn.Sequential(nn.ReLU(), nn.Linear(1024, 1024), nn.ReLU())
         self.regressor_ih = nn.Sequential(nn.Linear(1024 + self.total_params_dim, self.total_params_dim))
         self.hand_classifier = nn.Sequential(nn.Linear(1024, 2))
+        self.encoder_precision = getattr(opt, "encoder_precision", "fp32")
+        if self.encoder_precision not in ENCODER_PRECISIONS:
+            raise ValueError(f"encoder_precision must be one of {ENCODER_PRECISIONS}, not {self.encoder_precision!r}")
         self._packed = None
+        self._packed_bf16 = None
         self.main_feat = None
 
     def load_state_dict(self, *a, **k):
         self._packed = None
+        self._packed_bf16 = None
         return super().load_state_dict(*a, **k)
+
+    def _trunk_layers(self):
+        """(key, conv, bn, stride, pad) of every conv of the ResNet-50 trunk after the stem."""
+        for li in range(1, 5):
+            for bi, blk in enumerate(getattr(self.main_encoder, f"layer{li}")):
+                for ci, (conv, bn, st, pd) in enumerate([(blk.conv1, blk.bn1, 1, 0), (blk.conv2, blk.bn2, blk.stride, 1),
+                                                        (blk.conv3, blk.bn3, 1, 0)], start=1):
+                    yield f"l{li}.{bi}.c{ci}", conv, bn, st, pd
+                if blk.downsample is not None:
+                    yield f"l{li}.{bi}.ds", blk.downsample[0], blk.downsample[1], blk.stride, 0
+
+    def _pack_bf16(self, dev):
+        """The trunk's weights for the bf16 path: the same fp32 fold as ``_pack``, then one rounding to bf16 (``_PackedBF16``)."""
+        me = self.main_encoder
+        t = lambda x: x.to(dev)
+        w, b = _fold_bn(me.conv1, me.bn1)
+        P = {"stem": _PackedBF16(t(w), t(b), stride=2, pad=3, k_extra=1)}
+        for key, conv, bn, st, pd in self._trunk_layers():
+            w, b = _fold_bn(conv, bn)
+            P[key] = _PackedBF16(t(w), t(b), stride=st, pad=pd)
+        self._packed_bf16 = P
+
+    def _trunk_bf16(self, main_input):
+        """Stem through layer4 + AvgPool2d(7) + ReLU on the bf16 path; returns the fp32 pooled feature [B][2048]."""
+        dev = main_input.device
+        if self._packed_bf16 is None or self._packed_bf16["stem"].w.device != dev:
+            self._pack_bf16(dev)
+        P = self._packed_bf16
+        B, C, H, W = main_input.shape
+        assert C == 3
+        L = hip.lib()
+        img = main_input if main_input.dtype == torch.float32 and main_input.is_contiguous() else main_input.float().contiguous()
+        # NCHW fp32 -> NHWC bf16, 3 -> 4 channels, in one launch; one staging buffer per launch stream (as the fp32 path's)
+        cache = self.__dict__.setdefault("_nhwc4_bf16", {})
+        skey = torch.cuda.current_stream(dev).cuda_stream
+        x = cache.get(skey)
+        if x is None or x.shape[:3] != (B, H, W) or x.device != dev:
+            x = cache[skey] = torch.empty(B, H, W, 4, device=dev, dtype=torch.bfloat16)
+        hip.check(L.ihmr_pack_image_bf16(hip.ptr(img), hip.ptr(x), B, H, W, hip.stream_ptr()), "ihmr_pack_image_bf16")
+        y, H, W = conv_igemm_bf16(x, P["stem"], B, H, W, ldx=4, act=1)
+        Hp, Wp = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
+        xp = torch.empty(B * Hp * Wp, 64, device=dev, dtype=torch.bfloat16)
+        hip.check(L.ihmr_maxpool3x3s2_bf16(hip.ptr(y), hip.ptr(xp), B, H, W, 64, Hp, Wp, hip.stream_ptr()), "ihmr_maxpool3x3s2_bf16")
+        x, H, W, cin = xp, Hp, Wp, 64
+        for li in range(1, 5):
+            for bi, blk in enumerate(getattr(self.main_encoder, f"layer{li}")):
+                k = f"l{li}.{bi}"
+                y1, H1, W1 = conv_igemm_bf16(x, P[k + ".c1"], B, H, W, ldx=cin, act=1)
+                y2, H2, W2 = conv_igemm_bf16(y1, P[k + ".c2"], B, H1, W1, ldx=P[k + ".c1"].cout, act=1)
+                if blk.downsample is not None:
+                    res, _, _ = conv_igemm_bf16(x, P[k + ".ds"], B, H, W, ldx=cin, act=0)
+                else:
+                    res = x
+                cout = P[k + ".c3"].cout
+                x, H, W = conv_igemm_bf16(y2, P[k + ".c3"], B, H2, W2, ldx=P[k + ".c2"].cout, residual=res, ldr=cout, act=1)
+                cin = cout
+        pooled = torch.empty(B, 2048, device=dev)
+        hip.check(L.ihmr_avgpool_relu_bf16(hip.ptr(x), hip.ptr(pooled), B, H * W, 2048, 2048, hip.stream_ptr()), "ihmr_avgpool_relu_bf16")
+        return pooled
 
     def _pack(self, dev):
         P = {}
@@ -131,7 +243,7 @@ class InterHandEncoder(nn.Module):
         t = lambda x: x.to(dev)
         w, b = _fold_bn(me.conv1, me.bn1)
         P["stem"] = _Packed(t(w), t(b), stride=2, pad=3, k_extra=1)   # the image is padded to 4 channels: 16-byte gathers (csrc/encoder.h: CONV_C4)
-        for li in range(1, 5):
+        for li in range(1, 5 if self.encoder_precision == "fp32" else 1):   # (the bf16 path packs its own trunk: _pack_bf16)
             for bi, blk in enumerate(getattr(me, f"layer{li}")):
                 for ci, (conv, bn, st, pd) in enumerate([(blk.conv1, blk.bn1, 1, 0), (blk.conv2, blk.bn2, blk.stride, 1),
                                                         (blk.conv3, blk.bn3, 1, 0)], start=1):
@@ -154,36 +266,40 @@ class InterHandEncoder(nn.Module):
         if self._packed is None or self._packed["stem"].w.device != dev:
             self._pack(dev)
         P = self._packed
-        B, C, H, W = main_input.shape
-        # NHWC, 3 -> 4 channels (layout plumbing only); channel 3 stays zero.  One staging buffer per launch stream: two forwards of one
-        # module on two streams (two instances in flight share the weights) must not write the same buffer
-        cache = self.__dict__.setdefault("_nhwc4", {})
-        skey = torch.cuda.current_stream(dev).cuda_stream
-        x = cache.get(skey)
-        if x is None or x.shape[:3] != (B, H, W) or x.device != dev:
-            x = cache[skey] = torch.zeros(B, H, W, 4, device=dev)
-        x[..., :3].copy_(main_input.permute(0, 2, 3, 1))
-        # stem: conv 7x7/2 + BN + ReLU, max-pool 3x3/2
-        y, H, W = conv_igemm(x, P["stem"], B, H, W, ldx=4, act=1)
-        Hp, Wp = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
-        xp = torch.empty(B * Hp * Wp, 64, device=dev)
-        hip.check(hip.lib().ihmr_maxpool3x3s2(hip.ptr(y), hip.ptr(xp), B, H, W, 64, Hp, Wp, hip.stream_ptr()), "ihmr_maxpool3x3s2")
-        x, H, W, cin = xp, Hp, Wp, 64
-        for li in range(1, 5):
-            for bi, blk in enumerate(getattr(self.main_encoder, f"layer{li}")):
-                k = f"l{li}.{bi}"
-                y1, H1, W1 = conv_igemm(x, P[k + ".c1"], B, H, W, ldx=cin, act=1)
-                y2, H2, W2 = conv_igemm(y1, P[k + ".c2"], B, H1, W1, ldx=P[k + ".c1"].cout, act=1)
-                if blk.downsample is not None:
-                    res, _, _ = conv_igemm(x, P[k + ".ds"], B, H, W, ldx=cin, act=0)
-                else:
-                    res = x
-                cout = P[k + ".c3"].cout
-                x, H, W = conv_igemm(y2, P[k + ".c3"], B, H2, W2, ldx=P[k + ".c2"].cout, residual=res, ldr=cout, act=1)
-                cin = cout
-        # AvgPool2d(7) + ReLU, fc1 + ReLU  (resnet.py:149-154)
-        pooled = torch.empty(B, 2048, device=dev)
-        hip.check(hip.lib().ihmr_avgpool_relu(hip.ptr(x), hip.ptr(pooled), B, H * W, 2048, 2048, hip.stream_ptr()), "ihmr_avgpool_relu")
+        B = main_input.shape[0]
+        if self.encoder_precision == "bf16":
+            pooled = self._trunk_bf16(main_input)
+        else:
+            B, C, H, W = main_input.shape
+            # NHWC, 3 -> 4 channels (layout plumbing only); channel 3 stays zero.  One staging buffer per launch stream: two forwards of one
+            # module on two streams (two instances in flight share the weights) must not write the same buffer
+            cache = self.__dict__.setdefault("_nhwc4", {})
+            skey = torch.cuda.current_stream(dev).cuda_stream
+            x = cache.get(skey)
+            if x is None or x.shape[:3] != (B, H, W) or x.device != dev:
+                x = cache[skey] = torch.zeros(B, H, W, 4, device=dev)
+            x[..., :3].copy_(main_input.permute(0, 2, 3, 1))
+            # stem: conv 7x7/2 + BN + ReLU, max-pool 3x3/2
+            y, H, W = conv_igemm(x, P["stem"], B, H, W, ldx=4, act=1)
+            Hp, Wp = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
+            xp = torch.empty(B * Hp * Wp, 64, device=dev)
+            hip.check(hip.lib().ihmr_maxpool3x3s2(hip.ptr(y), hip.ptr(xp), B, H, W, 64, Hp, Wp, hip.stream_ptr()), "ihmr_maxpool3x3s2")
+            x, H, W, cin = xp, Hp, Wp, 64
+            for li in range(1, 5):
+                for bi, blk in enumerate(getattr(self.main_encoder, f"layer{li}")):
+                    k = f"l{li}.{bi}"
+                    y1, H1, W1 = conv_igemm(x, P[k + ".c1"], B, H, W, ldx=cin, act=1)
+                    y2, H2, W2 = conv_igemm(y1, P[k + ".c2"], B, H1, W1, ldx=P[k + ".c1"].cout, act=1)
+                    if blk.downsample is not None:
+                        res, _, _ = conv_igemm(x, P[k + ".ds"], B, H, W, ldx=cin, act=0)
+                    else:
+                        res = x
+                    cout = P[k + ".c3"].cout
+                    x, H, W = conv_igemm(y2, P[k + ".c3"], B, H2, W2, ldx=P[k + ".c2"].cout, residual=res, ldr=cout, act=1)
+                    cin = cout
+            # AvgPool2d(7) + ReLU, fc1 + ReLU  (resnet.py:149-154)
+            pooled = torch.empty(B, 2048, device=dev)
+            hip.check(hip.lib().ihmr_avgpool_relu(hip.ptr(x), hip.ptr(pooled), B, H * W, 2048, 2048, hip.stream_ptr()), "ihmr_avgpool_relu")
         main_feat, _, _ = conv_igemm(pooled, P["fc1"], B, 1, 1, ldx=2048, act=1)
         self.main_feat = main_feat
         # feat_encoder = ReLU (no-op on a ReLU output), Linear, ReLU; written into the IEF input buffers [feat | params | 0]

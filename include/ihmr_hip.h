@@ -261,6 +261,34 @@ int ihmr_conv_igemm(const float* x, const float* w, const float* bias, const flo
 int ihmr_maxpool3x3s2(const float* x, float* y, int N, int H, int W, int C, int Ho, int Wo, void* stream);
 int ihmr_avgpool_relu(const float* x, float* y, int N, int HW, int C, int ldy, void* stream);
 
+/* ---- opt-in bf16 form of the ResNet-50 trunk (InterHandEncoder with encoder_precision = "bf16"; no counterpart in the reference, whose
+ * users get reduced precision from torch.autocast).  bf16 values are passed as their 16-bit patterns (uint16_t).
+ * One Conv2d + folded BatchNorm (+ residual) (+ ReLU) as an implicit GEMM on the bf16 matrix cores with fp32 accumulation:
+ *   y[M = N*Ho*Wo][Cout] = bf16( act( A(x) . w  + bias  (+ residual) ) ),  the sum, the bias, the residual and act in fp32, ONE
+ *   round-to-nearest-even at the store (the bits of torch's `.bfloat16()`).
+ * x: NHWC bf16, pixel stride ldx elements;  w: bf16 [ceil32(kh*kw*Cin) / 8][ldw][8] -- element (k, n) of the K-major matrix at
+ * ((k / 8) * ldw + n) * 8 + k % 8, BatchNorm folded in fp32 before the rounding, zero padded, 16-byte aligned, ldw a multiple of 64 (128 to
+ * use the wide tile) and >= Cout rounded up to the tile width;  bias fp32 [Cout] (16-byte aligned) or NULL;  residual optional bf16
+ * [M][ldr];  y bf16 [M][ldy];  act: 0 none, 1 ReLU (anything else is refused).
+ * Gather forms (chosen by shape): Cin % 32 == 0, ldx % 8 == 0, Cin <= 4096, x 16-byte aligned: one 16-byte load per 8 channels, one
+ * filter tap per K step of 32; Cin == ldx == 4 (an image padded from 3 channels): two 8-byte pixel loads per 8 k; anything else: a scalar
+ * gather.  Epilogue: 8-byte accesses when Cout, ldy, ldr are multiples of 4 and y, residual 8-byte aligned, else element by element.
+ * workspace (optional, device, workspace_bytes): fp32 scratch for partial sums.  A layer with fewer than two 128-row tiles per CU and
+ * at least 8 K steps splits its K loop over up to min(8, workspace_bytes / (M*Cout*4)) workgroups; a second launch adds the pieces in
+ * ascending K order and applies the epilogue.  Results are bit-identical from run to run; the split follows the device's CU count, so
+ * they are bit-stable per device model, and differ in the last bit with and without a workspace. */
+int ihmr_conv_igemm_bf16(const uint16_t* x, const uint16_t* w, const float* bias, const uint16_t* residual, uint16_t* y, int N, int H,
+                         int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int ldx, int ldw, int ldy,
+                         int ldr, int act, void* workspace, size_t workspace_bytes, void* stream);
+/* img: NCHW fp32 [N][3][H][W] -> y: NHWC bf16 [N][H][W][4], channel 3 zero, round-to-nearest-even; y 8-byte aligned */
+int ihmr_pack_image_bf16(const float* img, uint16_t* y, int N, int H, int W, void* stream);
+/* nn.MaxPool2d(3, stride 2, padding 1) on NHWC bf16 (exact), C % 8 == 0, 16-byte aligned */
+int ihmr_maxpool3x3s2_bf16(const uint16_t* x, uint16_t* y, int N, int H, int W, int C, int Ho, int Wo, void* stream);
+/* AvgPool2d over the whole HW-pixel map + ReLU: bf16 in [N][HW][C], fp32 sum in pixel order, fp32 out [N][ldy]; C % 8 == 0 */
+int ihmr_avgpool_relu_bf16(const uint16_t* x, float* y, int N, int HW, int C, int ldy, void* stream);
+/* y[i] = bf16(x[i]), round-to-nearest-even (every NaN becomes 0x7FC0, as in torch), i < n */
+int ihmr_cast_f32_bf16(const float* x, uint16_t* y, size_t n, void* stream);
+
 /* ------------------------------------------------------------------ evaluation metrics */
 /* Per-sample partial results of the four metrics `optimize.py:98-102` prints (utils/metric_utils.py:23-38,107-143,
  * utils/evaluator.py:149-181), computed on the device from what `get_pred_result()` would export:

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Secondary workloads (BASELINE.json configs[1], configs[2]): IHMR-Baseline B=64 and IHMR-MLP B=128 inference.
-Not the driver's bench line (that is bench.py = IHMR-OPT); prints one JSON line per workload."""
+Not the driver's bench line (that is bench.py = IHMR-OPT); prints one JSON line per workload.
+`baseline --precision fp32|bf16|both`: the encoder precision of IHMR-Baseline (default fp32: the line as before; bf16 / both: one line per
+precision with `encoder_precision`, the repetitions and, for bf16, the algorithmic-bytes figure against the HBM peak)."""
 import json, os, sys, time, types
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -18,14 +20,96 @@ def timeit(fn, steps, warmup):
     for _ in range(steps): fn()
     torch.cuda.synchronize(); return (time.perf_counter() - t0) / steps
 
+def encoder_algorithmic_bytes(B, res=224):
+    """Bytes the bf16 trunk has to move per pass if every activation is written once and read once per consumer and every packed
+    weight is read once (bf16: 2 bytes; the image read as fp32, the pooled feature written as fp32) -- from the layer shapes alone."""
+    total = B * 3 * res * res * 4 + B * res * res * 4 * 2 * 2            # image in, NHWC4 bf16 staging written + read
+    H = res // 2
+    total += 7 * 7 * 4 * 64 * 2 + B * H * H * 64 * 2 * 2                   # stem weights, stem output written + read by the max-pool
+    H //= 2
+    cin, act = 64, B * H * H * 64 * 2                                      # the max-pool's output (bytes); written below with its readers
+    total += act
+    for planes, blocks, stride in [(64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2)]:
+        for b in range(blocks):
+            st = stride if b == 0 else 1
+            Ho = H // st
+            x_bytes = B * H * H * cin * 2
+            y1, y2, y3 = B * H * H * planes * 2, B * Ho * Ho * planes * 2, B * Ho * Ho * planes * 4 * 2
+            total += x_bytes + y1 + cin * planes * 2                       # conv1: read x, write y1, weights
+            total += y1 + y2 + 9 * planes * planes * 2                     # conv2
+            if b == 0:
+                total += x_bytes + y3 + cin * planes * 4 * 2               # downsample: read x, write the residual, weights
+            total += y2 + y3 + y3 + planes * planes * 4 * 2                # conv3: read y2, read the residual, write the block's output
+            cin, H = planes * 4, Ho
+    total += B * H * H * cin * 2 + B * cin * 4                             # avg-pool: read, write fp32
+    return total
+
+
+def bench_baseline(precisions):
+    """IHMR-Baseline B = 64 for each precision; with more than one, the timings alternate between the models (after both warmed up)
+    five times each, so that clock and temperature drift hit both alike."""
+    from ihmr_amd import two_hand
+    from ihmr_amd.baseline_model import InterHandModel
+    from ihmr_amd.synthetic import synthetic_opt_batch
+    B, HBM_PEAK = 64, 8.0e12
+    models = {p: InterHandModel(opt(B, encoder_precision=p)).eval() for p in precisions}
+    m0 = models[precisions[0]]
+    fwd = lambda p, s, t: two_hand.forward_from_packed(m0.mano_models["right"], p.cuda(), s.cuda(), t.cuda())[2]
+    batch = {k: v.cuda() for k, v in synthetic_opt_batch(B, fwd, seed=1234, with_image=True).items()}
+    pend = {p: [] for p in precisions}
+
+    def step_async(p):        # the export of batch i is collected while batch i + 1 runs (get_pred_result_async)
+        m = models[p]
+        m.set_input(batch); m.test(); pend[p].append(m.get_pred_result_async())
+        if len(pend[p]) > 1: pend[p].pop(0).wait()
+    reps = {p: dict(step=[], enc=[]) for p in precisions}
+    for p in precisions:                                   # warm-up of every model: packing, workspaces, graph capture
+        timeit(lambda: step_async(p), 3, 3); timeit(lambda: models[p].encoder(batch["img"]), 3, 3)
+    for _ in range(5):
+        for p in precisions:
+            reps[p]["step"].append(timeit(lambda: step_async(p), 20, 2))
+            reps[p]["enc"].append(timeit(lambda: models[p].encoder(batch["img"]), 10, 2))
+    out = {}
+    for p in precisions:
+        dt, enc = float(np.median(reps[p]["step"])), float(np.median(reps[p]["enc"]))
+        d = dict(workload="IHMR-Baseline (ResNet-50 + MANO regress) batch=64 inference", encoder_precision=p, images_per_s=B / dt, ms_per_batch=dt * 1e3,
+                 encoder_ms_per_batch=enc * 1e3, encoder_ms_per_batch_reps=[round(t * 1e3, 4) for t in reps[p]["enc"]],
+                 images_per_s_reps=[round(B / t, 1) for t in reps[p]["step"]], encoder_tflops=8.2e9 * B / enc / 1e12)
+        if p == "bf16":
+            nbytes = encoder_algorithmic_bytes(B)
+            d.update(encoder_algorithmic_bytes=nbytes, encoder_algorithmic_bytes_per_s=nbytes / enc,
+                     encoder_frac_of_hbm_peak=nbytes / enc / HBM_PEAK,
+                     bound="HBM: algorithmic bytes (bf16 activations written once and read once per consumer + packed weights) over the 8 TB/s peak")
+        else:
+            d.update(encoder_frac_of_fp32_mfma_peak=8.2e9 * B / enc / 157.3e12)
+        out[p] = d
+    if len(precisions) > 1:
+        f, b = reps["fp32"], reps["bf16"]
+        for p in precisions:
+            out[p]["bf16_slowest_faster_than_fp32_fastest"] = dict(encoder=max(b["enc"]) < min(f["enc"]), step=max(b["step"]) < min(f["step"]))
+            out[p]["encoder_time_ratio_bf16_over_fp32"] = out["bf16"]["encoder_ms_per_batch"] / out["fp32"]["encoder_ms_per_batch"]
+    for p in precisions:
+        print(json.dumps(out[p]))
+
+
 def main():
     from ihmr_amd import two_hand
     from ihmr_amd.baseline_model import InterHandModel
     from ihmr_amd.mlp_model import MLPModel
     from ihmr_amd.strategies import make_mlp_strategy
     from ihmr_amd.synthetic import synthetic_opt_batch
-    which = sys.argv[1:] or ["baseline", "mlp", "train"]
-    if "baseline" in which:
+    argv = sys.argv[1:]
+    precision = "fp32"                                     # --precision fp32|bf16|both (baseline only; fp32 = the output as before)
+    if "--precision" in argv:
+        i = argv.index("--precision")
+        precision = argv[i + 1]
+        del argv[i:i + 2]
+        if precision not in ("fp32", "bf16", "both"):
+            raise SystemExit("--precision fp32|bf16|both")
+    which = argv or ["baseline", "mlp", "train"]
+    if "baseline" in which and precision != "fp32":
+        bench_baseline(["fp32", "bf16"] if precision == "both" else [precision])
+    elif "baseline" in which:
         B = 64
         m = InterHandModel(opt(B)); m.eval()
         fwd = lambda p, s, t: two_hand.forward_from_packed(m.mano_models["right"], p.cuda(), s.cuda(), t.cuda())[2]
