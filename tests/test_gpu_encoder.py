@@ -50,8 +50,20 @@ def test_conv_igemm_matches_torch(cfg):
 def test_conv_streamk_matches_torch(cfg):
     """The Stream-K form of the 128 x 128 tile (csrc/encoder.h: conv_streamk_kernel + conv_streamk_fixup_kernel) on shapes that
     select it (ihmr_conv_igemm: >= 64 K steps, 64..768 tiles), with residual + ReLU in both epilogues, and bit-identical on a re-run
-    (the partial sums are added in a fixed order)."""
+    (the partial sums are added in a fixed order).  That the launcher did select it is asserted, not assumed: the workspace is filled
+    with a NaN bit pattern before each launch and the words that changed must be exactly the (worker, slot) 64 KB slots the restated
+    launcher and partition (tests/encoder_shapes.py, tests/test_streamk_partition.py) predict for this device's CU count -- for the
+    fourth case (62 tiles, below the limit) the ksplit x M x Cout prefix of the split-K path instead."""
+    import encoder_shapes as E
+    from test_gpu_encoder_shapes import NAN32, _footprint_errors, _workspace
     from ihmr_amd.networks import _Packed, conv_igemm
+    shape = E.Shape("small", cfg["N"], cfg["H"], cfg["W"], cfg["Cin"], cfg["Cout"], cfg["k"], cfg["s"], cfg["p"], cfg["Cin"], cfg["Cout"],
+                    cfg["Cout"], cfg["res"], 1, ())
+    plan = E.plan_fp32(shape, torch.cuda.get_device_properties(0).multi_processor_count)
+    footprint = E.workspace_footprint(shape, plan)
+    if torch.cuda.get_device_properties(0).multi_processor_count == 256:
+        assert [plan["streamk"], plan["ksplit"]] == ([False, 18] if cfg["s"] == 2 else [True, 1]), plan
+        assert not plan["streamk"] or E.streamk_slots(plan)[1] == (cfg["N"] == 96)      # only the second case has workers that own whole tiles
     g = torch.Generator().manual_seed(5)
     x = torch.randn(cfg["N"], cfg["Cin"], cfg["H"], cfg["W"], generator=g)
     w = torch.randn(cfg["Cout"], cfg["Cin"], cfg["k"], cfg["k"], generator=g) / np.sqrt(cfg["Cin"] * cfg["k"] ** 2)
@@ -65,8 +77,16 @@ def test_conv_streamk_matches_torch(cfg):
         res = torch.randn(cfg["N"] * Ho * Wo, cfg["Cout"], generator=g).cuda()
         ref = ref + res.view(cfg["N"], Ho, Wo, cfg["Cout"]).permute(0, 3, 1, 2)
     ref = torch.relu(ref).cpu()
-    y, _, _ = conv_igemm(xn, pk, cfg["N"], cfg["H"], cfg["W"], ldx=cfg["Cin"], residual=res, ldr=cfg["Cout"], act=1)
-    y2, _, _ = conv_igemm(xn, pk, cfg["N"], cfg["H"], cfg["W"], ldx=cfg["Cin"], residual=res, ldr=cfg["Cout"], act=1)
+    wsi = _workspace()
+    outs = []
+    for _ in range(2):
+        wsi.fill_(NAN32)
+        outs.append(conv_igemm(xn, pk, cfg["N"], cfg["H"], cfg["W"], ldx=cfg["Cin"], residual=res, ldr=cfg["Cout"], act=1)[0])
+        torch.cuda.synchronize()
+        wrong = _footprint_errors(wsi, footprint)
+        print(f"[parity] stream-K conv {cfg}: form={plan['form']} workspace words off the predicted footprint={wrong}")
+        assert wrong == 0, (plan, wrong)
+    y, y2 = outs
     assert torch.equal(y, y2)
     got = y.view(cfg["N"], Ho, Wo, cfg["Cout"]).permute(0, 3, 1, 2).cpu()
     _report(f"stream-K conv {cfg}", got, ref, atol=3e-5, rtol=1e-5)
