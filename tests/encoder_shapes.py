@@ -20,20 +20,28 @@ from test_streamk_partition import worker_pieces  # noqa: E402
 WORKSPACE_BYTES = 128 * 1024 * 1024          # networks._splitk_workspace
 SLOT_FLOATS = 128 * 128                      # one Stream-K tile slot (64 KB)
 
-Shape = collections.namedtuple("Shape", "name N H W Cin Cout k stride pad ldx ldy ldr residual act also")
+Shape = collections.namedtuple("Shape", "name N H W Cin Cout k stride pad ldx ldy ldr residual act also kh kw Ho Wo", defaults=(None,) * 4)
 # ldx / ldy / ldr: the strides networks.py passes; residual: the network adds one; act: the network's activation (0 none, 1 ReLU,
 # 2 sigmoid); also: the later layers of the same geometry.  Heads: y (and the residual) of `reg` start at column HEAD_COL of the
-# ldy-wide buffer.
+# ldy-wide buffer.  kh, kw (default k, k) and Ho, Wo (default: the convolution formula) describe the launches of the training backward
+# pass (tests/encoder_train_shapes.py): non-square phase filters with the output map given by the caller.
 HEAD_COL = 1024
 
 
+def filter_hw(s):
+    return (s.k, s.k) if s.kh is None else (s.kh, s.kw)
+
+
 def out_hw(s):
+    if s.Ho is not None:
+        return s.Ho, s.Wo
     return (s.H + 2 * s.pad - s.k) // s.stride + 1, (s.W + 2 * s.pad - s.k) // s.stride + 1
 
 
 def gemm_dims(s):
     Ho, Wo = out_hw(s)
-    return s.N * Ho * Wo, s.k * s.k * s.Cin
+    kh, kw = filter_hw(s)
+    return s.N * Ho * Wo, kh * kw * s.Cin
 
 
 @functools.lru_cache(maxsize=None)
@@ -137,7 +145,7 @@ def plan_fp32(s, cus, workspace_bytes=WORKSPACE_BYTES, y_aligned16=True):
     if (fast and pick == 0 and M > 64 and s.Cout % 128 == 0 and s.ldy % 4 == 0 and y_aligned16 and 64 <= sk_tiles <= 768 and nk >= 64
             and sk_tiles * nk >= 4 * workers and workspace_bytes >= workers * 2 * SLOT_FLOATS * 4):
         return dict(tile=(128, 128), mode="fast", ksplit=1, streamk=True, workers=workers, tiles=sk_tiles, nk=nk, reduce=None, form="streamk")
-    mode = "fast" if fast else "c4" if (s.Cin == 4 and s.ldx % 4 == 0 and s.k >= 4 and not wide_ok) else "generic"
+    mode = "fast" if fast else "c4" if (s.Cin == 4 and s.ldx % 4 == 0 and filter_hw(s)[1] >= 4 and not wide_ok) else "generic"
     if mode == "c4" and pick != 2:
         tile = (64, 64)
     else:
