@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <mutex>
 #include <vector>
 
@@ -21,6 +22,7 @@
 #include "train.h"
 #include "train_conv.h"
 #include "copy_pack.h"
+#include "launch_plan.h"
 
 // bench.py's per-kernel timer -- the library's ONE piece of process-global state (include/ihmr_hip.h says so): the pointer and the
 // list of pending event pairs are shared by every stream and thread of the process, guarded by g_timer_mutex; while no timer is set
@@ -313,7 +315,6 @@ extern "C" int ihmr_mano_lbs_bwd(const ihmr_mano* m, int N, const void* workspac
 // Compute units of the CURRENT device, cached per device id in relaxed atomics (concurrent first calls store the same value: no lock, no
 // data race).  The persistent grid of sdf_dist_kernel and the Stream-K worker count of ihmr_conv_igemm derive from it; the latter fixes
 // the K partition, so results are bit-stable per device MODEL (same CU count), not across models.
-#include <atomic>
 static int device_cu_count(int* cus_out) {
     static std::atomic<int> cache[64];
     int dev = 0;
@@ -781,107 +782,58 @@ extern "C" int ihmr_opt_sdf_inside_bits(const ihmr_opt_io* io, int B, unsigned* 
 }
 
 // ------------------------------------------------------------------------------------------ encoder
+// The tile kernels of a launcher, looked up by what its planner (csrc/launch_plan.h) chose; a plan without an entry is an error
+template <typename Args>
+struct TileKernel { int bm, bn, mode; void (*kernel)(Args); };
+template <typename Args, size_t n>
+static void (*tile_kernel(const TileKernel<Args> (&table)[n], int bm, int bn, int mode))(Args) {
+    for (const TileKernel<Args>& e : table)
+        if (e.bm == bm && e.bn == bn && e.mode == mode) return e.kernel;
+    return nullptr;
+}
+static_assert(plan::CONV_BK_F32 == CONV_BK && plan::CONV_BK_BF16 == CONVB_BK, "launch_plan.h restates the K steps of the conv kernels");
+static_assert(plan::GENERIC == CONV_GENERIC && plan::FAST == CONV_FAST && plan::C4 == CONV_C4, "launch_plan.h restates the gather modes");
+static_assert(plan::GENERIC == CONVB_GENERIC && plan::FAST == CONVB_FAST && plan::C4 == CONVB_C4, "launch_plan.h restates the gather modes");
+
+static const TileKernel<ConvArgs> kConvKernels[] = {
+    {128, 128, CONV_FAST, conv_igemm_kernel<128, 128, CONV_FAST>},       {64, 128, CONV_FAST, conv_igemm_kernel<64, 128, CONV_FAST>},
+    {128, 64, CONV_FAST, conv_igemm_kernel<128, 64, CONV_FAST>},         {64, 64, CONV_FAST, conv_igemm_kernel<64, 64, CONV_FAST>},
+    {128, 64, CONV_C4, conv_igemm_kernel<128, 64, CONV_C4>},             {64, 64, CONV_C4, conv_igemm_kernel<64, 64, CONV_C4>},
+    {128, 128, CONV_GENERIC, conv_igemm_kernel<128, 128, CONV_GENERIC>}, {64, 128, CONV_GENERIC, conv_igemm_kernel<64, 128, CONV_GENERIC>},
+    {128, 64, CONV_GENERIC, conv_igemm_kernel<128, 64, CONV_GENERIC>},   {64, 64, CONV_GENERIC, conv_igemm_kernel<64, 64, CONV_GENERIC>}};
+
 extern "C" int ihmr_conv_igemm(const float* x, const float* w, const float* bias, const float* residual, float* y, int N, int H,
                                int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int ldx, int ldw,
                                int ldy, int ldr, int act, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !w || !y || N <= 0 || Cout <= 0) return -1;
-    ConvArgs a{x, w, bias, residual, y, N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, ldx, ldw, ldy, ldr, act, (float*)workspace, 1};
-    const int M = N * Ho * Wo, nk = (kh * kw * Cin + CONV_BK - 1) / CONV_BK;
+    if (!x || !w || !y) return -1;
     hipStream_t st = (hipStream_t)stream;
-    // Tile and K split, from per-layer measurements on MI355X (scripts/prof_encoder.py with IHMR_CONV_FORCE):
-    // the 128 x 128 tile wins on every ResNet-50 layer, even when it leaves CUs without a workgroup -- smaller
-    // tiles move twice the operands through LDS per MFMA.  Occupancy is repaired with split-K instead: layers with
-    // fewer than 1.5 workgroups per CU and a long K loop run their K halves in separate workgroups (two resident
-    // workgroups per CU also hide each other's barriers); partial sums go to the caller's workspace and
-    // conv_splitk_reduce_kernel adds them in fixed order.  Single-image-row layers (the Linear layers at batch 64)
-    // take the 64-row tile and the deepest split the K loop allows.
-    const bool wide_ok = Cout > 64 && ldw % 128 == 0;
-    if (!wide_ok && ldw % 64 != 0) return -1;
-    const int tiles[4][2] = {{128, 128}, {64, 128}, {128, 64}, {64, 64}};
-    auto blocks = [&](int t) { return (long)((M + tiles[t][0] - 1) / tiles[t][0]) * ((Cout + tiles[t][1] - 1) / tiles[t][1]); };
-    auto usable = [&](int t) { return tiles[t][1] == 64 || wide_ok; };
-    const long cap = workspace ? (long)(workspace_bytes / ((size_t)M * Cout * sizeof(float))) : 1;
-    int pick = wide_ok ? 0 : 2, ksplit = 1;
-    // Linear layers (a handful of workgroups): every K step costs a global-load round trip (~1 us) that nothing hides at this
-    // occupancy, so the K loop is cut as deep as 4 steps per workgroup allow (measured on the IHMR-MLP training step:
-    // 8-way 0.47 ms, 16-way 0.41 ms, 32-way 0.39 ms per step)
-    if (M <= 64) {
-        pick = wide_ok ? 1 : 3;
-        ksplit = (int)std::max<long>(1, std::min<long>(std::min<long>(32, cap), nk / 4));
-    } else if (blocks(pick) < 64) {
-        ksplit = (int)std::max<long>(1, std::min<long>(std::min<long>(32, cap), nk / 4));
-    } else if (blocks(pick) < 384 && nk >= 64 && cap >= 2) {
-        ksplit = 2;
-    } else if (wide_ok && blocks(0) > 768 && blocks(0) < 896) {
-        // 784 tiles (the 14 x 14 layers with >= 1024 output channels): three resident workgroups per CU take 768, the last 16 run alone at ~2 us
-        // per K step (8-33 us: scripts/experiments/conv_tail_generation.py); as 1568 half-height tiles (six resident per CU) the stragglers
-        // are half as long.  Measured per layer (scripts/experiments/tile_sweep.sh): 145 -> 132 us (32 K steps), 82 -> 77.5 us (16 K steps)
-        pick = 1;
-    }
+    int cus = 0;
+    if (int rc = device_cu_count(&cus)) return rc;
+    plan::ConvTuning tuning;
 #ifdef IHMR_TUNING_BUILD   // per-layer tile / split measurements (scripts/prof_encoder.py builds its own library with this macro)
-    if (const char* force = getenv("IHMR_CONV_FORCE")) {   // "<tile 0-3> <ksplit>"
-        int ft = -1, fk = 1;
-        if (sscanf(force, "%d %d", &ft, &fk) >= 1 && ft >= 0 && ft < 4 && usable(ft)) {
-            pick = ft;
-            ksplit = (int)std::max<long>(1, std::min<long>(std::min<long>(fk, cap), std::max(1, nk / 4)));
-        }
-    }
-#endif
-    a.ksplit = ksplit;
-    const bool fast = (Cin % CONV_BK) == 0 && (ldx % 4) == 0 && Cin <= 2048;   // (2048: the zero page the padding pixels are read from, csrc/encoder.h)
-    // Stream-K (csrc/encoder.h): layers with a long K loop and at most three 128 x 128 tiles per CU -- at batch 64 every 3 x 3 layer and the
-    // first 1 x 1 of every bottleneck from 28 x 28 down (100, 196 or 392 tiles: 0.4-1.5 per CU) -- are shared evenly by two workers per CU.
-    // Measured per layer (scripts/prof_encoder_layers.sh, round 4): 3 x 3 layers 175-187 -> 144-158 us, 1 x 1 layers with K >= 1024
-    // 90-155 -> 77-141 us; with 32 K steps the fix-up's traffic eats the gain (85 -> 88 us), so those keep one workgroup per tile.
-    // Workers: two per CU of THIS device, a multiple of 8 (conv_streamk_kernel numbers them by XCD), at most 512 (the workspace
-    // contract of include/ihmr_hip.h: two 64 KB tile slots per worker = 64 MiB)
-    int sk_cus = 0;
-    if (int rc = device_cu_count(&sk_cus)) return rc;
-    int sk_workers = std::max(8, std::min(512, 2 * sk_cus / 8 * 8)), sk_max_tiles = 768, sk_min_nk = 64;
-#ifdef IHMR_TUNING_BUILD
+    if (const char* force = getenv("IHMR_CONV_FORCE")) sscanf(force, "%d %d", &tuning.force_tile, &tuning.force_ksplit);   // "<tile 0-3> <ksplit>"
     if (const char* f = getenv("IHMR_CONV_SK")) {   // "<max tiles> <min K steps> <workers>"
-        sscanf(f, "%d %d %d", &sk_max_tiles, &sk_min_nk, &sk_workers);
-        if (sk_workers < 8 || sk_workers % 8 != 0) return -1;
+        tuning.sk_workers = plan::streamk_workers(cus);
+        sscanf(f, "%d %d %d", &tuning.sk_max_tiles, &tuning.sk_min_nk, &tuning.sk_workers);
+        if (tuning.sk_workers < 8 || tuning.sk_workers % 8 != 0) return -1;
     }
 #endif
-    const long sk_tiles = blocks(0);
-    if (fast && pick == 0 && M > 64 && Cout % 128 == 0 && ldy % 4 == 0 && ((uintptr_t)y % 16) == 0 && sk_tiles >= 64 && sk_tiles <= sk_max_tiles && nk >= sk_min_nk &&
-        sk_tiles * nk >= 4L * sk_workers && workspace && workspace_bytes >= (size_t)sk_workers * 2 * 128 * 128 * sizeof(float)) {
-        const int tiles_m = (M + 127) / 128, total = (int)(sk_tiles * nk);
-        hipLaunchKernelGGL(conv_streamk_kernel, dim3(sk_workers), dim3(512), 0, st, a, tiles_m, nk, total);
-        hipLaunchKernelGGL(conv_streamk_fixup_kernel, dim3((unsigned)sk_tiles, 8), dim3(256), 0, st, a, tiles_m, nk, total, sk_workers);
+    const plan::ConvPlan p = plan::plan_conv_fp32(N, Cin, Ho, Wo, Cout, kh, kw, ldx, ldw, ldy, cus, workspace ? workspace_bytes : 0,
+                                                  ((uintptr_t)y % 16) == 0, tuning);
+    if (!p.ok) return -1;
+    ConvArgs a{x, w, bias, residual, y, N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, ldx, ldw, ldy, ldr, act, (float*)workspace, p.ksplit};
+    if (p.streamk) {
+        const int total = p.sk_tiles * p.nk;
+        hipLaunchKernelGGL(conv_streamk_kernel, dim3(p.sk_workers), dim3(512), 0, st, a, p.tiles_m, p.nk, total);
+        hipLaunchKernelGGL(conv_streamk_fixup_kernel, dim3((unsigned)p.sk_tiles, 8), dim3(256), 0, st, a, p.tiles_m, p.nk, total, p.sk_workers);
         return (int)hipGetLastError();
     }
-    // (a persistent 1-D grid walking the tiles with a stride -- the cure for sdf_dist_kernel's slow slot refill -- was measured here too:
-    // 6.95 -> 7.17 ms per 64-image pass at 6, 5 and 4 waves per SIMD alike; one workgroup per tile stays)
-    const dim3 grid((M + tiles[pick][0] - 1) / tiles[pick][0], (Cout + tiles[pick][1] - 1) / tiles[pick][1], ksplit);
-    if (fast) {
-        switch (pick) {
-            case 0: hipLaunchKernelGGL((conv_igemm_kernel<128, 128, CONV_FAST>), grid, dim3(512), 0, st, a); break;
-            case 1: hipLaunchKernelGGL((conv_igemm_kernel<64, 128, CONV_FAST>), grid, dim3(256), 0, st, a); break;
-            case 2: hipLaunchKernelGGL((conv_igemm_kernel<128, 64, CONV_FAST>), grid, dim3(256), 0, st, a); break;
-            default: hipLaunchKernelGGL((conv_igemm_kernel<64, 64, CONV_FAST>), grid, dim3(128), 0, st, a); break;
-        }
-    } else if (Cin == 4 && (ldx % 4) == 0 && kw >= 4 && !wide_ok) {      // the stem on the image padded to 4 channels
-        if (pick == 2) hipLaunchKernelGGL((conv_igemm_kernel<128, 64, CONV_C4>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv_igemm_kernel<64, 64, CONV_C4>), grid, dim3(128), 0, st, a);
-    } else {
-        switch (pick) {
-            case 0: hipLaunchKernelGGL((conv_igemm_kernel<128, 128, CONV_GENERIC>), grid, dim3(512), 0, st, a); break;
-            case 1: hipLaunchKernelGGL((conv_igemm_kernel<64, 128, CONV_GENERIC>), grid, dim3(256), 0, st, a); break;
-            case 2: hipLaunchKernelGGL((conv_igemm_kernel<128, 64, CONV_GENERIC>), grid, dim3(256), 0, st, a); break;
-            default: hipLaunchKernelGGL((conv_igemm_kernel<64, 64, CONV_GENERIC>), grid, dim3(128), 0, st, a); break;
-        }
-    }
-    if (ksplit > 1) {
-        if (Cout % 4 == 0) {
-            const long total = (long)M * (Cout / 4);
-            hipLaunchKernelGGL(conv_splitk_reduce_kernel<4>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
-        } else {
-            const long total = (long)M * Cout;
-            hipLaunchKernelGGL(conv_splitk_reduce_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
-        }
-    }
+    void (*kernel)(ConvArgs) = tile_kernel(kConvKernels, p.bm, p.bn, p.mode);
+    if (!kernel) return -1;
+    hipLaunchKernelGGL(kernel, dim3(p.grid_x, p.grid_y, p.grid_z), dim3(p.threads), 0, st, a);
+    const long M = (long)N * Ho * Wo;
+    if (p.reduce == 4) hipLaunchKernelGGL(conv_splitk_reduce_kernel<4>, dim3((unsigned)((M * (Cout / 4) + 255) / 256)), dim3(256), 0, st, a);
+    else if (p.reduce == 1) hipLaunchKernelGGL(conv_splitk_reduce_kernel<1>, dim3((unsigned)((M * Cout + 255) / 256)), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
 
@@ -898,44 +850,30 @@ extern "C" int ihmr_avgpool_relu(const float* x, float* y, int N, int HW, int C,
 }
 
 // ---- bf16 encoder path (csrc/encoder_bf16.h)
+static const TileKernel<ConvArgsBF16> kConvKernelsBF16[] = {
+    {128, 128, CONVB_FAST, conv_igemm_bf16_kernel<128, CONVB_FAST>}, {128, 128, CONVB_C4, conv_igemm_bf16_kernel<128, CONVB_C4>},
+    {128, 128, CONVB_GENERIC, conv_igemm_bf16_kernel<128, CONVB_GENERIC>},
+    {128, 64, CONVB_FAST, conv_igemm_bf16_kernel<64, CONVB_FAST>},   {128, 64, CONVB_C4, conv_igemm_bf16_kernel<64, CONVB_C4>},
+    {128, 64, CONVB_GENERIC, conv_igemm_bf16_kernel<64, CONVB_GENERIC>}};
+
 extern "C" int ihmr_conv_igemm_bf16(const uint16_t* x, const uint16_t* w, const float* bias, const uint16_t* residual, uint16_t* y, int N,
                                     int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int ldx,
                                     int ldw, int ldy, int ldr, int act, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !w || !y || N <= 0 || Cout <= 0 || Cin <= 0 || (act != 0 && act != 1) || ldw % 64 != 0 || ldw < Cout) return -1;
+    if (!x || !w || !y) return -1;
     if (((uintptr_t)w % 16) != 0 || (bias && ((uintptr_t)bias % 16) != 0)) return -1;
-    const int M = N * Ho * Wo, nk = (kh * kw * Cin + CONVB_BK - 1) / CONVB_BK;
     hipStream_t st = (hipStream_t)stream;
-    const bool wide = Cout > 64 && ldw % 128 == 0;
-    const int BN = wide ? 128 : 64;
-    if (ldw < (Cout + BN - 1) / BN * BN) return -1;
-    const int vec = Cout % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)y % 8) == 0 && (!residual || (ldr % 4 == 0 && ((uintptr_t)residual % 8) == 0));
-    ConvArgsBF16 a{x, w, bias, residual, y, N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, ldx, ldw, ldy, ldr, act, (float*)workspace, 1, vec};
-    // K split: a layer with fewer than two tiles per CU (at batch 64: the 14 x 14 and 7 x 7 stages) runs its K loop in up to 8 pieces of
-    // at least 4 steps; the pieces' fp32 sums go to the workspace and are added in ascending K order (bit-identical from run to run;
-    // the split follows the device's CU count, so results are bit-stable per device model)
     int cus = 0;
     if (int rc = device_cu_count(&cus)) return rc;
-    const long tiles = (long)((M + 127) / 128) * ((Cout + BN - 1) / BN);
-    int ksplit = 1;
-    if (workspace && tiles < 2L * cus && nk >= 8) {
-        const long cap = (long)(workspace_bytes / ((size_t)M * Cout * sizeof(float)));
-        ksplit = (int)std::max<long>(1, std::min<long>(std::min<long>(8, cap), std::min<long>(nk / 4, (2L * cus + tiles - 1) / tiles)));
-    }
-    a.ksplit = ksplit;
-    const dim3 grid((M + 127) / 128, (Cout + BN - 1) / BN, ksplit), block(256);
-    const int mode = (Cin % CONVB_BK == 0 && ldx % 8 == 0 && Cin <= 4096 && ((uintptr_t)x % 16) == 0) ? CONVB_FAST
-                   : (Cin == 4 && ldx == 4 && ((uintptr_t)x % 8) == 0) ? CONVB_C4 : CONVB_GENERIC;
-    if (wide) {
-        if (mode == CONVB_FAST) hipLaunchKernelGGL((conv_igemm_bf16_kernel<128, CONVB_FAST>), grid, block, 0, st, a);
-        else if (mode == CONVB_C4) hipLaunchKernelGGL((conv_igemm_bf16_kernel<128, CONVB_C4>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((conv_igemm_bf16_kernel<128, CONVB_GENERIC>), grid, block, 0, st, a);
-    } else {
-        if (mode == CONVB_FAST) hipLaunchKernelGGL((conv_igemm_bf16_kernel<64, CONVB_FAST>), grid, block, 0, st, a);
-        else if (mode == CONVB_C4) hipLaunchKernelGGL((conv_igemm_bf16_kernel<64, CONVB_C4>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((conv_igemm_bf16_kernel<64, CONVB_GENERIC>), grid, block, 0, st, a);
-    }
-    if (ksplit > 1) {
-        const long total = (long)M * ((Cout + 3) / 4);
+    const plan::ConvPlanBF16 p = plan::plan_conv_bf16(N, Cin, Ho, Wo, Cout, kh, kw, ldx, ldw, ldy, ldr, act, cus, workspace ? workspace_bytes : 0,
+                                                      ((uintptr_t)x % 16) == 0, ((uintptr_t)x % 8) == 0, ((uintptr_t)y % 8) == 0,
+                                                      residual != nullptr, ((uintptr_t)residual % 8) == 0);
+    if (!p.ok) return -1;
+    ConvArgsBF16 a{x, w, bias, residual, y, N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, ldx, ldw, ldy, ldr, act, (float*)workspace, p.ksplit, p.vec};
+    void (*kernel)(ConvArgsBF16) = tile_kernel(kConvKernelsBF16, 128, p.bn, p.mode);
+    if (!kernel) return -1;
+    hipLaunchKernelGGL(kernel, dim3(p.grid_x, p.grid_y, p.grid_z), dim3(256), 0, st, a);
+    if (p.ksplit > 1) {
+        const long total = (long)N * Ho * Wo * ((Cout + 3) / 4);
         hipLaunchKernelGGL(conv_splitk_reduce_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
     }
     return (int)hipGetLastError();
@@ -968,7 +906,6 @@ extern "C" int ihmr_cast_f32_bf16(const float* x, uint16_t* y, size_t n, void* s
     return (int)hipGetLastError();
 }
 
-// ------------------------------------------------------------------------------------------ misc
 // ------------------------------------------------------------------------------------------ evaluator
 extern "C" int ihmr_eval_metrics(const float* pred_joints_3d, const float* gt_joints_3d, const float* coll_origin_scale,
                                  const float* sample_scale, const unsigned char* interacting, int B, double* out6, void* stream) {
@@ -1041,12 +978,6 @@ extern "C" int ihmr_adam_step(float* params, const float* grads, float* exp_avg,
 }
 
 // ------------------------------------------------------------------------------------------ encoder training kernels
-#define BN_MAX_CHUNKS 1024
-static int bn_chunks(long M, int* rows_per) {
-    long rp = std::max<long>(16, (M + BN_MAX_CHUNKS - 1) / BN_MAX_CHUNKS);
-    *rows_per = (int)rp;
-    return (int)((M + rp - 1) / rp);
-}
 static dim3 bn_grid(int C, int S) { return dim3((unsigned)((C / 4 + 255) / 256), (unsigned)S); }
 
 extern "C" size_t ihmr_bn_workspace_bytes(int C) { return (size_t)BN_MAX_CHUNKS * 2 * C * sizeof(float) + (size_t)2 * C * sizeof(float); }
@@ -1056,8 +987,8 @@ extern "C" int ihmr_bn_train_forward(const float* z, long M, int C, const float*
                                      float* running_var, float momentum, void* workspace, void* stream) {
     if (!z || !gamma || !beta || !y || !mean || !var || !invstd || !workspace || M <= 0 || C <= 0 || C % 4) return -1;
     hipStream_t st = (hipStream_t)stream;
-    int rows_per;
-    const int S = bn_chunks(M, &rows_per);
+    const plan::BnChunks ch = plan::plan_bn_chunks(M);
+    const int S = ch.chunks, rows_per = ch.rows_per;
     float* part = (float*)workspace;
     const dim3 grid = bn_grid(C, S);
     // two passes over z: sum z -> mean (chunks added in double), then sum (z - mean)^2 -> biased variance / invstd / running statistics
@@ -1079,8 +1010,8 @@ extern "C" int ihmr_bn_train_backward(const float* z, const float* g, long M, in
                                       void* stream) {
     if (!z || !g || !mean || !invstd || !gamma || !dz || !dgamma || !dbeta || !workspace || M <= 0 || C <= 0 || C % 4) return -1;
     hipStream_t st = (hipStream_t)stream;
-    int rows_per;
-    const int S = bn_chunks(M, &rows_per);
+    const plan::BnChunks ch = plan::plan_bn_chunks(M);
+    const int S = ch.chunks, rows_per = ch.rows_per;
     float* part = (float*)workspace;
     // sum g -> dbeta, sum g * xhat -> dgamma (written by the finish kernel itself, read back by the apply kernel)
     hipLaunchKernelGGL(bn_partial_kernel<2>, bn_grid(C, S), dim3(256), 0, st, z, g, (int)M, C, C, C, rows_per, mean, invstd, part, relu_y);
@@ -1091,35 +1022,27 @@ extern "C" int ihmr_bn_train_backward(const float* z, const float* g, long M, in
     return (int)hipGetLastError();
 }
 
+static const TileKernel<WgradArgs> kWgradKernels[] = {{128, 128, 0, conv_wgrad_kernel<128, 128>}, {128, 64, 0, conv_wgrad_kernel<128, 64>},
+                                                      {64, 128, 0, conv_wgrad_kernel<64, 128>},   {64, 64, 0, conv_wgrad_kernel<64, 64>}};
+
 extern "C" int ihmr_conv_wgrad(const float* x, const float* dy, float* dw, int N, int H, int W, int Cin, int Ho, int Wo, int Cout,
                                int kh, int kw, int stride, int pad, int ldx, int lddy, int ldw, void* workspace,
                                size_t workspace_bytes, void* stream) {
-    if (!x || !dy || !dw || !workspace || N <= 0 || Cin % 4 || lddy % 4 || ldx % 4 || ldw < Cout) return -1;
+    if (!x || !dy || !dw || !workspace) return -1;
     hipStream_t st = (hipStream_t)stream;
-    // (conv_wgrad_kernel splits a pixel index by a float-reciprocal product with a +-1 correction: exact below 2^23 pixels)
-    if ((long)N * Ho * Wo >= (1L << 23)) return -1;
-    const int M = N * Ho * Wo, K = kh * kw * Cin;
-    const bool wide_n = Cout > 64, wide_m = K > 64;
-    const int BMv = wide_m ? 128 : 64, BNv = wide_n ? 128 : 64;
-    const long tiles = (long)((K + BMv - 1) / BMv) * ((Cout + BNv - 1) / BNv);
-    const int nchunks = (M + CONV_BK - 1) / CONV_BK;
-    const long cap = (long)(workspace_bytes / ((size_t)K * Cout * sizeof(float)));
-    if (cap < 1) return -1;
-    long msplit = std::max<long>(1, std::min<long>(std::min<long>(cap, 256), std::min<long>((1024 + tiles - 1) / tiles, std::max(1, nchunks / 8))));
-    const int chunks_per = (int)((nchunks + msplit - 1) / msplit);
-    msplit = (nchunks + chunks_per - 1) / chunks_per;
-    WgradArgs a{x, dy, (float*)workspace, N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, ldx, lddy, chunks_per};
-    const dim3 grid((K + BMv - 1) / BMv, (Cout + BNv - 1) / BNv, (unsigned)msplit);
-    if (wide_m && wide_n) hipLaunchKernelGGL((conv_wgrad_kernel<128, 128>), grid, dim3(512), 0, st, a);
-    else if (wide_m) hipLaunchKernelGGL((conv_wgrad_kernel<128, 64>), grid, dim3(256), 0, st, a);
-    else if (wide_n) hipLaunchKernelGGL((conv_wgrad_kernel<64, 128>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<64, 64>), grid, dim3(128), 0, st, a);
+    const plan::WgradPlan p = plan::plan_conv_wgrad(N, Cin, Ho, Wo, Cout, kh, kw, ldx, lddy, ldw, workspace_bytes);
+    if (!p.ok) return -1;
+    const int K = kh * kw * Cin;
+    WgradArgs a{x, dy, (float*)workspace, N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, ldx, lddy, p.chunks_per};
+    void (*kernel)(WgradArgs) = tile_kernel(kWgradKernels, p.bm, p.bn, 0);
+    if (!kernel) return -1;
+    hipLaunchKernelGGL(kernel, dim3(p.grid_x, p.grid_y, p.grid_z), dim3(p.threads), 0, st, a);
     // fixed-order sum of the pixel-range partials into dw [K][ldw]
-    ConvArgs r{nullptr, nullptr, nullptr, nullptr, dw, K, 1, 1, 0, 1, 1, Cout, 1, 1, 1, 0, 0, 0, ldw, 0, 0, (float*)workspace, (int)msplit};
-    if (Cout % 4 == 0 && ldw % 4 == 0 && msplit >= 32)
+    ConvArgs r{nullptr, nullptr, nullptr, nullptr, dw, K, 1, 1, 0, 1, 1, Cout, 1, 1, 1, 0, 0, 0, ldw, 0, 0, (float*)workspace, p.msplit};
+    if (p.reduce == plan::WGRAD_REDUCE)
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(((long)K * (Cout / 4) + 15) / 16)), dim3(256), 0, st, (const float*)workspace, dw, K,
-                           Cout, ldw, (int)msplit);
-    else if (Cout % 4 == 0) hipLaunchKernelGGL(conv_splitk_reduce_kernel<4>, dim3((unsigned)(((long)K * (Cout / 4) + 255) / 256)), dim3(256), 0, st, r);
+                           Cout, ldw, p.msplit);
+    else if (p.reduce == plan::WGRAD_SPLITK4) hipLaunchKernelGGL(conv_splitk_reduce_kernel<4>, dim3((unsigned)(((long)K * (Cout / 4) + 255) / 256)), dim3(256), 0, st, r);
     else hipLaunchKernelGGL(conv_splitk_reduce_kernel<1>, dim3((unsigned)(((long)K * Cout + 255) / 256)), dim3(256), 0, st, r);
     return (int)hipGetLastError();
 }

@@ -60,7 +60,7 @@ def test_batchnorm_train_forward_backward(N, C, H, W, res, relu):
 
 
 def _bn_rows_per_chunk(M):
-    """bn_chunks() of ihmr_hip.hip: rows per chunk of the BatchNorm column reductions (BN_MAX_CHUNKS = 1024, at least 16)."""
+    """plan_bn_chunks() of csrc/launch_plan.h: rows per chunk of the BatchNorm column reductions (BN_MAX_CHUNKS = 1024, at least 16)."""
     return max(16, -(-M // 1024))
 
 
