@@ -6,8 +6,8 @@ forward (``baseline_model.py:257-282``): encoder (ResNet-50 + IEF head on the ma
 122-vector ``[cam 3 | pose 96 | shape 20 | trans 3]`` (``:262-270``) -> MANO for predicted AND ground-truth
 parameters with SEPARATE right / left models, no mirroring (``:208-254``) -> orthographic projection;
 ``test()`` (``:350-355``) adds the collision term for the metric.  The training step (``forward_train`` /
-``optimize_parameters``, ``src/train_baseline.py:75-80``) is in :mod:`ihmr_amd.baseline_train`; visualisation is out of
-scope.
+``optimize_parameters``, ``src/train_baseline.py:75-80``) is in :mod:`ihmr_amd.baseline_train`, the training-time augmentation
+of its input batches (``BaselineDataset.preprocess_data``) in :mod:`ihmr_amd.augment`; visualisation is out of scope.
 """
 from __future__ import annotations
 

@@ -14,6 +14,7 @@
 #include "mano_lbs.h"
 #include "sdf_collision.h"
 #include "preprocess.h"
+#include "augment.h"
 #include "mlp_infer.h"
 #include "refine.h"
 #include "encoder.h"
@@ -1095,7 +1096,62 @@ extern "C" int ihmr_preprocess_images(const uint8_t* pixels, const int64_t* offs
     if (!pixels || !offsets || !sizes || !img_out || B <= 0 || final_size <= 0 || final_size % PRE_PPT || (joints_in && !joints_out))
         return -1;
     hipLaunchKernelGGL(preprocess_kernel, dim3((final_size * final_size / PRE_PPT + PRE_THREADS - 1) / PRE_THREADS, B), dim3(PRE_THREADS), 0,
-                       (hipStream_t)stream, pixels, offsets, sizes, do_flip, final_size, img_out, img_u8, joints_in, joints_out);
+                       (hipStream_t)stream, pixels, offsets, sizes, do_flip, final_size, img_out, img_u8, joints_in, joints_out, 1);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------ training-time augmentation
+extern "C" int ihmr_augment_images(const uint8_t* pixels, const int64_t* offsets, const int32_t* sizes, const ihmr_aug_params* params,
+                                   int B, int final_size, int steps, const float* blur_bank, const int32_t* blur_dims, int n_blur,
+                                   uint8_t* buf0, uint8_t* buf1, uint32_t* gray_sums, float* img_out, int* final_buffer, void* stream) {
+    const int S = final_size;
+    if (!pixels || !offsets || !sizes || !params || !buf0 || !buf1 || !img_out || !final_buffer || B <= 0 || S <= 0 || S % PRE_PPT || S > 4096)
+        return -1;
+    if ((steps & IHMR_AUG_COLOR) && !gray_sums) return -1;
+    if ((steps & IHMR_AUG_BLUR) && (!blur_bank || !blur_dims || n_blur <= 0)) return -1;
+    const hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((S * S / PRE_PPT + AUG_THREADS - 1) / AUG_THREADS, B), block(AUG_THREADS);
+    int left = !!(steps & IHMR_AUG_RESCALE) + !!(steps & IHMR_AUG_ROTATE) + !!(steps & IHMR_AUG_COLOR) + !!(steps & IHMR_AUG_BLUR);
+    uint8_t *cur = buf0, *nxt = buf1;
+    // pad, resize, flip: the test-time kernel through its uint8 output; it writes the float planes itself when no step follows
+    hipLaunchKernelGGL(preprocess_kernel, grid, block, 0, st, pixels, offsets, sizes, reinterpret_cast<const uint8_t*>(&params->flip), S,
+                       left ? (float*)nullptr : img_out, cur, (const float*)nullptr, (float*)nullptr, (int)sizeof(ihmr_aug_params));
+    if (steps & IHMR_AUG_RESCALE) {
+        hipLaunchKernelGGL(aug_rescale_kernel, grid, block, 0, st, cur, nxt, --left ? (float*)nullptr : img_out, params, S);
+        std::swap(cur, nxt);
+    }
+    if (steps & IHMR_AUG_ROTATE) {
+        hipLaunchKernelGGL(aug_rotate_kernel, grid, block, 0, st, cur, nxt, --left ? (float*)nullptr : img_out, params, S);
+        std::swap(cur, nxt);
+    }
+    if (steps & IHMR_AUG_COLOR) {
+        if (hipMemsetAsync(gray_sums, 0, sizeof(uint32_t) * (size_t)B, st) != hipSuccess) return (int)hipGetLastError();
+        hipLaunchKernelGGL(aug_gray_sum_kernel, grid, block, 0, st, cur, params, S, gray_sums);
+        hipLaunchKernelGGL(aug_color_kernel, grid, block, 0, st, cur, nxt, --left ? (float*)nullptr : img_out, params, S, gray_sums);
+        std::swap(cur, nxt);
+    }
+    if (steps & IHMR_AUG_BLUR) {
+        const int tiles = (S + AUG_BLUR_TILE - 1) / AUG_BLUR_TILE;
+        hipLaunchKernelGGL(aug_blur_kernel, dim3(tiles * tiles, B), block, 0, st, cur, nxt, --left ? (float*)nullptr : img_out, params, S,
+                           blur_bank, blur_dims, n_blur);
+        std::swap(cur, nxt);
+    }
+    *final_buffer = cur == buf0 ? 0 : 1;
+    return (int)hipGetLastError();
+}
+
+extern "C" int ihmr_augment_labels(const int32_t* sizes, const ihmr_aug_params* params, int B, int final_size, const float* joints_2d,
+                                   const float* joints_3d, const float* mano_pose, const float* mano_betas, const float* mano_params_weight,
+                                   const float* hand_type_array, float* out_joints_2d, float* out_joints_3d, float* out_mano_pose,
+                                   float* out_mano_betas, float* out_mano_params_weight, float* out_hand_type_array, float* out_do_flip,
+                                   float* out_hand_trans, void* stream) {
+    if (!sizes || !params || B <= 0 || final_size <= 0 || !joints_2d || !joints_3d || !mano_pose || !mano_betas || !mano_params_weight ||
+        !hand_type_array || !out_joints_2d || !out_joints_3d || !out_mano_pose || !out_mano_betas || !out_mano_params_weight ||
+        !out_hand_type_array || !out_do_flip || !out_hand_trans)
+        return -1;
+    hipLaunchKernelGGL(aug_labels_kernel, dim3(B), dim3(AUG_LABEL_THREADS), 0, (hipStream_t)stream, sizes, params, final_size, joints_2d,
+                       joints_3d, mano_pose, mano_betas, mano_params_weight, hand_type_array, out_joints_2d, out_joints_3d, out_mano_pose,
+                       out_mano_betas, out_mano_params_weight, out_hand_type_array, out_do_flip, out_hand_trans);
     return (int)hipGetLastError();
 }
 

@@ -70,14 +70,15 @@ __device__ __forceinline__ PreImage pre_geometry(int H, int W, int S) {
 __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(const uint8_t* __restrict__ pixels, const int64_t* __restrict__ offsets,
                                                                  const int32_t* __restrict__ sizes, const uint8_t* __restrict__ do_flip,
                                                                  int S, float* __restrict__ img_out, uint8_t* __restrict__ img_u8,
-                                                                 const float* __restrict__ joints_in, float* __restrict__ joints_out) {
+                                                                 const float* __restrict__ joints_in, float* __restrict__ joints_out,
+                                                                 int flip_stride) {
     __shared__ PreImage gsh;
     const int b = blockIdx.y;
     if (threadIdx.x == 0) gsh = pre_geometry(sizes[2 * b], sizes[2 * b + 1], S);
     __syncthreads();
     const PreImage g = gsh;
     const int H = g.H, W = g.W, nh = g.nh, nw = g.nw;
-    const bool flip = do_flip && do_flip[b];
+    const bool flip = do_flip && do_flip[(size_t)b * flip_stride];  // (the augmentation reads its parameter table's flip field)
 
     if (joints_in && blockIdx.x == 0 && threadIdx.x < 42) {
         const int j = threadIdx.x;
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(const uint8_t* 
     const size_t plane = (size_t)S * S;
     float* o = img_out + (size_t)b * 3 * plane + (size_t)oy * S + ox0;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {                                     // ToTensor, Normalize(0.5, 0.5)
+    for (int c = 0; c < 3 && img_out; ++c) {                          // ToTensor, Normalize(0.5, 0.5); skipped by the augmentation chain
         float4 f;
         f.x = ((float)v[0][c] / 255.0f - 0.5f) / 0.5f; f.y = ((float)v[1][c] / 255.0f - 0.5f) / 0.5f;
         f.z = ((float)v[2][c] / 255.0f - 0.5f) / 0.5f; f.w = ((float)v[3][c] / 255.0f - 0.5f) / 0.5f;

@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = [
     "ihmr_dilate2", "ihmr_interleave2", "ihmr_pack_dgrad_weight", "ihmr_maxpool3x3s2_backward", "ihmr_avgpool_relu_backward", "ihmr_set_kernel_timer", "ihmr_flush_kernel_timer",
     "ihmr_mlp_workspace_bytes", "ihmr_mlp_stage_head", "ihmr_mlp_forward_select", "ihmr_mlp_camera_select", "ihmr_opt_forward_verts",
     "ihmr_debug_force_lbs_bwd2_streaming", "ihmr_debug_force_full_skin", "ihmr_version", "ihmr_copy_segments", "ihmr_root_align_joints",
+    "ihmr_augment_images", "ihmr_augment_labels",
     "ihmr_conv_igemm_bf16", "ihmr_pack_image_bf16", "ihmr_maxpool3x3s2_bf16", "ihmr_avgpool_relu_bf16", "ihmr_cast_f32_bf16",
 ]
 
@@ -297,6 +298,8 @@ def lib():
         L.ihmr_maxpool3x3s2_backward.argtypes = [vp, vp, vp, i, i, i, i, i, i, vp]
         L.ihmr_avgpool_relu_backward.argtypes = [vp, vp, vp, i, i, i, i, vp]
         L.ihmr_preprocess_images.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp]
+        L.ihmr_augment_images.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, i, vp, vp, vp, vp, C.POINTER(C.c_int), vp]
+        L.ihmr_augment_labels.argtypes = [vp, vp, i, i] + [vp] * 14 + [vp]
         L.ihmr_opt_sdf_stats.argtypes = [vp, vp, C.POINTER(OptIO), i, C.POINTER(OptWeights), vp, vp]
         L.ihmr_opt_sdf_counters.argtypes = [C.POINTER(OptIO), i, vp, i]
         L.ihmr_opt_sdf_inside_bits.argtypes = [C.POINTER(OptIO), i, vp, vp]

@@ -411,6 +411,50 @@ int ihmr_preprocess_images(const uint8_t* pixels, const int64_t* offsets, const 
                            int B, int final_size, float* img_out, uint8_t* img_u8, const float* joints_in,
                            float* joints_out, void* stream);
 
+/* ------------------------------------------------------------------ training-time augmentation of IHMR-Baseline
+ * The training-time half of `BaselineDataset.preprocess_data` (data/baseline_dataset.py:67-108) for a whole batch, in the reference's
+ * order: pad / resize / flip (data_preprocess.py:45-93), random rescale and position (:96-119), random rotation (:122-143,
+ * utils/rotate_utils.py), colour jitter (:146-152, torchvision 0.7 ColorJitter on PIL images), motion blur (:155-159, cv2.filter2D),
+ * ToTensor + Normalize (baseline_dataset.py:41-44,202).  Every image step quantises to uint8 as the reference does.
+ * The per-sample draws travel as ONE array of this struct (device memory, one copy): */
+#define IHMR_AUG_RESCALE 1
+#define IHMR_AUG_ROTATE 2
+#define IHMR_AUG_COLOR 4
+#define IHMR_AUG_BLUR 8      /* a step of the chain only; per sample the blur switch is blur_kernel >= 0 */
+typedef struct ihmr_aug_params {
+    double warp[6];          /* cv2.warpAffine's inverted 2x3 matrix (destination -> source) of getRotationMatrix2D((S/2, S/2), angle, 1) */
+    double rot_cos, rot_sin; /* cos / sin of -angle/180*pi in double (rotate_utils.rotate_joints_2d) */
+    float rot_z;             /* (float)(-pi*angle/180): the z rotation of rotate_orient / rotate_joints_3d */
+    float scale;             /* random_scale: joints_2d[:, :2] *= scale */
+    float brightness, contrast, saturation;   /* ColorJitter's factors */
+    int32_t flip;            /* 0 / 1: random_flip took place (left-only samples always) */
+    int32_t flags;           /* IHMR_AUG_RESCALE | IHMR_AUG_ROTATE | IHMR_AUG_COLOR: the steps this sample takes */
+    int32_t new_size, x_pos, y_pos;           /* int(S * scale) and the top-left corner on the zero canvas */
+    int32_t hue_shift;       /* (uint8)(int)(hue * 255) */
+    int32_t blur_kernel;     /* slot of the blur bank, -1 = no blur */
+    int32_t order[4];        /* order of 0 brightness, 1 contrast, 2 saturation, 3 hue */
+    float angle;             /* the drawn angle in degrees (for the host's records; the kernels read the derived fields above) */
+    int32_t reserved;
+} ihmr_aug_params;           /* 136 bytes */
+/* pixels / offsets / sizes as ihmr_preprocess_images takes them.  steps: which kernels run (IHMR_AUG_* bits; a sample whose own
+ * switch for a running step is off passes through it unchanged).  blur_bank (n_blur, 33*33) float32: the kh*kw taps of kernel k
+ * row-major at the head of slot k;  blur_dims (n_blur,2) int32 = kh, kw <= 33 (needed with IHMR_AUG_BLUR only).  buf0 / buf1:
+ * two (B,S,S,3) uint8 work buffers;  gray_sums (B) uint32 work (needed with IHMR_AUG_COLOR).  img_out (B,3,S,S) float32.
+ * *final_buffer (host) <- 0 / 1: which work buffer holds the final uint8 image.  S % 4 == 0, S <= 4096; with IHMR_AUG_RESCALE
+ * 1 <= new_size, x_pos + new_size <= S, y_pos + new_size <= S (the host wrapper checks). */
+int ihmr_augment_images(const uint8_t* pixels, const int64_t* offsets, const int32_t* sizes, const ihmr_aug_params* params, int B,
+                        int final_size, int steps, const float* blur_bank, const int32_t* blur_dims, int n_blur, uint8_t* buf0,
+                        uint8_t* buf1, uint32_t* gray_sums, float* img_out, int* final_buffer, void* stream);
+/* the label side of the same chain (data_preprocess.py:59,63-93,115-117,130-142,162-169; baseline_dataset.py:192-199): joints_2d
+ * (B,42,3) in source pixels -> [-1,1]; joints_3d (B,42,4); mano_pose (B,96); mano_betas (B,20) [all zero after a flip, as the
+ * reference returns them]; mano_params_weight, hand_type_array (B,2); out_do_flip (B) 0 / 1; out_hand_trans (B,1,4) from the
+ * augmented joints_3d.  One workgroup per sample. */
+int ihmr_augment_labels(const int32_t* sizes, const ihmr_aug_params* params, int B, int final_size, const float* joints_2d,
+                        const float* joints_3d, const float* mano_pose, const float* mano_betas, const float* mano_params_weight,
+                        const float* hand_type_array, float* out_joints_2d, float* out_joints_3d, float* out_mano_pose,
+                        float* out_mano_betas, float* out_mano_params_weight, float* out_hand_type_array, float* out_do_flip,
+                        float* out_hand_trans, void* stream);
+
 /* per-kernel timing hook for bench.py -- the ONE piece of mutable PROCESS-GLOBAL state of this library (everything else is stateless
  * apart from the model handle and a per-device cache of the CU count, relaxed atomics: concurrent first calls store the same value): the timer pointer and the pending event pairs are shared by every stream and every thread of the process
  * (a mutex makes concurrent callers safe, it does not separate their measurements); callers that do not set a timer never touch it.
