@@ -550,15 +550,13 @@ extern "C" int ihmr_opt_run_stage(const ihmr_mano* m, const ihmr_mano* m_left, c
             hipEvent_t tcur;
             const bool timed = g_timer != nullptr;
             if (timed) { if (int rc2 = timed_begin(&tcur, st)) return rc2; }
+            const TailArgs ta{*m, *io, wk, B, *w, vl, ws, need_cam, need_mask, next, ws.inside_count};
             if (vposed_fixed && it + 1 < sg->n_iters)
-                hipLaunchKernelGGL((opt_tail_kernel<true, true>), dim3(B), dim3(SDF_SAMPLE_THREADS), tail_lds, st, *m, *io, wk, B, *w, vl, ws, need_cam, need_mask,
-                                   next, ws.inside_count);
+                hipLaunchKernelGGL((opt_tail_kernel<true, true>), dim3(B), dim3(SDF_SAMPLE_THREADS), tail_lds, st, ta);
             else if (!pose_stage && it + 1 < sg->n_iters)
-                hipLaunchKernelGGL(opt_tail_kernel<true>, dim3(B), dim3(SDF_SAMPLE_THREADS), tail_lds, st, *m, *io, wk, B, *w, vl, ws, need_cam, need_mask,
-                                   next, ws.inside_count);
+                hipLaunchKernelGGL(opt_tail_kernel<true>, dim3(B), dim3(SDF_SAMPLE_THREADS), tail_lds, st, ta);
             else
-                hipLaunchKernelGGL(opt_tail_kernel<false>, dim3(B), dim3(SDF_SAMPLE_THREADS), tail_lds, st, *m, *io, wk, B, *w, vl, ws, need_cam, need_mask,
-                                   next, ws.inside_count);
+                hipLaunchKernelGGL(opt_tail_kernel<false>, dim3(B), dim3(SDF_SAMPLE_THREADS), tail_lds, st, ta);
             if (timed) { if (int rc2 = timed_next(&tcur, IHMR_TIMED_OPT_TAIL, st)) return rc2; (void)hipEventDestroy(tcur); }
             if (pose_stage)
                 lbs_backward_launch(m, true, 2 * B, B, wk.g_verts, wk.g_joints, wk.g_orient, wk.g_pose, wk.g_shape, wk.g_trans, need_mask,

@@ -433,21 +433,117 @@ struct LbsBwdShared {
     float wsum[LBS_THREADS / WAVE][4];
 };
 
+// ---- per vertex: d v_posed = T.R^T g, T.R = sum_j w_j A_j.R over all 16 joints (no branches: a zero weight adds
+//      an exact zero), the matrices read from LDS as broadcast rows.  Only the finger-pose and shape gradients need it.
+// By LBS_THREADS threads; sA = the hand's skinning matrices and g = its output gradients (raw hand frame), both in LDS.  The hand's
+// 2334 values go to dst_g (global memory: the workspace row lbs_bwd2 reads) and / or dst_l (LDS), whichever is not null; a thread reads
+// and writes its own vertices only.  LEAN (the fused tail, dense weights): one vertex's 16 weights at a time instead of all four
+// vertices' in flight together -- 64 registers that the tail does not have.
+template <bool LEAN>
+__device__ __forceinline__ void lbs_dvp_vertices(const ihmr_mano& m, const float* sA, const float* g, int tid, float* __restrict__ dst_g,
+                                                 float* dst_l) {
+    constexpr int VR = (NV + LBS_THREADS - 1) / LBS_THREADS;
+    auto put = [&](int v, const float (&T)[12]) {
+        const float g0 = g[3 * v], g1 = g[3 * v + 1], g2 = g[3 * v + 2];
+        float o[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = T[c] * g0 + T[4 + c] * g1 + T[8 + c] * g2;
+        if (dst_g) { dst_g[3 * v] = o[0]; dst_g[3 * v + 1] = o[1]; dst_g[3 * v + 2] = o[2]; }
+        if (dst_l) { dst_l[3 * v] = o[0]; dst_l[3 * v + 1] = o[1]; dst_l[3 * v + 2] = o[2]; }
+    };
+    if (m.sparse4) {
+        // the vertex's (up to) four non-zero weights (see lbs_skin_kernel): the same sums without their zero terms
+        float4 wr[VR];
+        uint32_t jr[VR];
+#pragma unroll
+        for (int r = 0; r < VR; ++r) {
+            const int v = min(tid + r * LBS_THREADS, NV - 1);
+            wr[r] = m.w4_w[v];
+            jr[r] = m.w4_j[v];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int r = 0; r < VR; ++r) {
+            const int v = tid + r * LBS_THREADS;
+            if (v >= NV) break;
+            const float wv[4] = {wr[r].x, wr[r].y, wr[r].z, wr[r].w};
+            float T[12];
+#pragma unroll
+            for (int e = 0; e < 12; ++e) T[e] = 0.f;
+#pragma unroll
+            for (int sI = 0; sI < 4; ++sI) {
+                const float4* A4 = reinterpret_cast<const float4*>(sA + 12 * (int)((jr[r] >> (8 * sI)) & 0xffu));
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const float4 a = A4[q];
+                    T[4 * q] = __builtin_fmaf(wv[sI], a.x, T[4 * q]);
+                    T[4 * q + 1] = __builtin_fmaf(wv[sI], a.y, T[4 * q + 1]);
+                    T[4 * q + 2] = __builtin_fmaf(wv[sI], a.z, T[4 * q + 2]);
+                }
+            }
+            put(v, T);
+        }
+    } else {
+        // the skinning weights of this thread's (up to 4) vertices, all 16 loads in flight together (L2 hits; the other three
+        // resident workgroups of the CU cover the round trip) -- LEAN: one vertex's four loads
+        constexpr int WR = LEAN ? 1 : VR, UNROLL = LEAN ? 1 : VR;
+        float4 wreg[WR][4];
+        if (!LEAN) {
+#pragma unroll
+            for (int r = 0; r < VR; ++r) {
+                const int v = min(tid + r * LBS_THREADS, NV - 1);
+                const float4* w4 = reinterpret_cast<const float4*>(m.weights + v * NJ);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) wreg[r % WR][q] = w4[q];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll UNROLL
+        for (int r = 0; r < VR; ++r) {
+            const int v = tid + r * LBS_THREADS;
+            if (v >= NV) break;
+            if (LEAN) {
+                const float4* w4 = reinterpret_cast<const float4*>(m.weights + v * NJ);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) wreg[0][q] = w4[q];
+            }
+            const float4* wq = wreg[r % WR];
+            const float w[NJ] = {wq[0].x, wq[0].y, wq[0].z, wq[0].w, wq[1].x, wq[1].y, wq[1].z, wq[1].w,
+                                 wq[2].x, wq[2].y, wq[2].z, wq[2].w, wq[3].x, wq[3].y, wq[3].z, wq[3].w};
+            float T[12];
+#pragma unroll
+            for (int e = 0; e < 12; ++e) T[e] = 0.f;
+#pragma unroll 4
+            for (int j = 0; j < NJ; ++j) {   // 4 joints' rows in flight: unrolled further the LDS reads alone take ~190 VGPRs
+                const float4* A4 = reinterpret_cast<const float4*>(sA + 12 * j);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const float4 a = A4[q];
+                    T[4 * q] = __builtin_fmaf(w[j], a.x, T[4 * q]);
+                    T[4 * q + 1] = __builtin_fmaf(w[j], a.y, T[4 * q + 1]);
+                    T[4 * q + 2] = __builtin_fmaf(w[j], a.z, T[4 * q + 2]);
+                }
+            }
+            put(v, T);
+        }
+    }
+}
+
 // dynamic LDS: float part[nseg][12] -- per-segment partial sums of dA (nseg is a property of the weight matrix:
 // 248 for 4 bones per vertex, up to LBS_SEG_CAP if dense); with it the workgroup needs ~38 KB: four fit a CU (1024 hands
 // = one round of the 256 CUs); d v_posed goes through the workspace (L2) instead of LDS for that
 // The backward of ONE hand by LBS_THREADS (256) threads tid = 0..255 (block-wide barriers inside: every thread of the workgroup
 // calls it, with its own hand's LDS).  lbs_bwd1_kernel = one hand per workgroup; opt_tail_kernel (refine.h) = both hands of a sample.
-template <bool TWO_HAND>
+template <bool TWO_HAND, bool IN_LDS = false>
 __device__ __forceinline__ void lbs_bwd1_hand(const ihmr_mano& m, const LbsWork& wk, int B, int h, int tid, LbsBwdShared& bw,
                                               float* bwd1_part /* [nseg][12], LDS */,
                                               const float* __restrict__ d_verts, const float* __restrict__ d_joints,
                                               float* __restrict__ d_orient, float* __restrict__ d_betas,
                                               float* __restrict__ d_trans, int need_mask, const LbsBwdShared* lds_left = nullptr) {
-    // lds_left != nullptr (opt_tail_kernel): the caller has already put this hand's inputs into `bw` -- g and gj (raw hand frame) written
+    // IN_LDS (opt_tail_kernel; lds_left = the left hand's record): the caller has already put this hand's inputs into `bw` -- g and gj (raw hand frame) written
     // by the sampling / loss phase of the same workgroup, vp and sk by DMA -- and passes the LEFT hand's record for d L / d shift;
     // nothing is read back from global memory and the staging phase is skipped.  The same values in the same order: the same bits.
-    const bool in_lds = TWO_HAND && lds_left != nullptr;
+    constexpr bool in_lds = TWO_HAND && IN_LDS;
     const bool left = TWO_HAND && h >= B;
     const int b = TWO_HAND ? (left ? h - B : h) : 0;
     const bool need_orient = need_mask & 1, need_pose = need_mask & 2, need_betas = need_mask & 4, need_trans = need_mask & 8;
@@ -599,6 +695,7 @@ __device__ __forceinline__ void lbs_bwd1_hand(const ihmr_mano& m, const LbsWork&
 #pragma unroll
                 for (int q = 0; q < 3; ++q) acc[3 * q + c] = __builtin_fmaf(g[q], d, acc[3 * q + c]);
             }
+            __builtin_amdgcn_sched_barrier(0);       // one vertex at a time: four vertices' rows in flight together do not fit the fused tail's registers
         }
 #pragma unroll
         for (int e = 0; e < 9; ++e) acc[e] = wave_reduce_sum_dpp(acc[e]);
@@ -630,83 +727,11 @@ __device__ __forceinline__ void lbs_bwd1_hand(const ihmr_mano& m, const LbsWork&
         return;
     }
 
-    // ---- per vertex: d v_posed = T.R^T g, T.R = sum_j w_j A_j.R over all 16 joints (no branches: a zero weight adds
-    //      an exact zero), the matrices read from LDS as broadcast rows.  Only the finger-pose and shape gradients need it.
-    if (need_pose || need_betas) {
-    if (m.sparse4) {
-        // the vertex's (up to) four non-zero weights (see lbs_skin_kernel): the same sums without their zero terms
-        float4 wr[VR];
-        uint32_t jr[VR];
-#pragma unroll
-        for (int r = 0; r < VR; ++r) {
-            const int v = min(tid + r * LBS_THREADS, NV - 1);
-            wr[r] = m.w4_w[v];
-            jr[r] = m.w4_j[v];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int r = 0; r < VR; ++r) {
-            const int v = tid + r * LBS_THREADS;
-            if (v >= NV) break;
-            const float wv[4] = {wr[r].x, wr[r].y, wr[r].z, wr[r].w};
-            float T[12];
-#pragma unroll
-            for (int e = 0; e < 12; ++e) T[e] = 0.f;
-#pragma unroll
-            for (int sI = 0; sI < 4; ++sI) {
-                const float4* A4 = reinterpret_cast<const float4*>(sA + 12 * (int)((jr[r] >> (8 * sI)) & 0xffu));
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const float4 a = A4[q];
-                    T[4 * q] = __builtin_fmaf(wv[sI], a.x, T[4 * q]);
-                    T[4 * q + 1] = __builtin_fmaf(wv[sI], a.y, T[4 * q + 1]);
-                    T[4 * q + 2] = __builtin_fmaf(wv[sI], a.z, T[4 * q + 2]);
-                }
-            }
-            const float g0 = bw.g[3 * v], g1 = bw.g[3 * v + 1], g2 = bw.g[3 * v + 2];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) wk.dvp[(size_t)h * NV3 + 3 * v + c] = T[c] * g0 + T[4 + c] * g1 + T[8 + c] * g2;
-        }
-    } else {
-    // the skinning weights of this thread's (up to 4) vertices, all 16 loads in flight together (L2 hits; the other three
-    // resident workgroups of the CU cover the round trip)
-    float4 wreg[VR][4];
-#pragma unroll
-    for (int r = 0; r < VR; ++r) {
-        const int v = min(tid + r * LBS_THREADS, NV - 1);
-        const float4* w4 = reinterpret_cast<const float4*>(m.weights + v * NJ);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) wreg[r][q] = w4[q];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int r = 0; r < VR; ++r) {
-        const int v = tid + r * LBS_THREADS;
-        if (v >= NV) break;
-        const float w[NJ] = {wreg[r][0].x, wreg[r][0].y, wreg[r][0].z, wreg[r][0].w, wreg[r][1].x, wreg[r][1].y, wreg[r][1].z, wreg[r][1].w,
-                             wreg[r][2].x, wreg[r][2].y, wreg[r][2].z, wreg[r][2].w, wreg[r][3].x, wreg[r][3].y, wreg[r][3].z, wreg[r][3].w};
-        float T[12];
-#pragma unroll
-        for (int e = 0; e < 12; ++e) T[e] = 0.f;
-#pragma unroll 4
-        for (int j = 0; j < NJ; ++j) {   // 4 joints' rows in flight: unrolled further the LDS reads alone take ~190 VGPRs
-            const float4* A4 = reinterpret_cast<const float4*>(sA + 12 * j);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const float4 a = A4[q];
-                T[4 * q] = __builtin_fmaf(w[j], a.x, T[4 * q]);
-                T[4 * q + 1] = __builtin_fmaf(w[j], a.y, T[4 * q + 1]);
-                T[4 * q + 2] = __builtin_fmaf(w[j], a.z, T[4 * q + 2]);
-            }
-        }
-        const float g0 = bw.g[3 * v], g1 = bw.g[3 * v + 1], g2 = bw.g[3 * v + 2];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            wk.dvp[(size_t)h * NV3 + 3 * v + c] = T[c] * g0 + T[4 + c] * g1 + T[8 + c] * g2;
-        }
-    }
-    }
-    }
+    // ---- per vertex: d v_posed (lbs_dvp_vertices).  Only the finger-pose and shape gradients need it.  The stand-alone kernel and a
+    //      fused tail without a shape gradient send it through the workspace row that lbs_bwd2 reads; a fused tail WITH a shape gradient
+    //      computes it further down, once v_posed is dead, and keeps it in LDS (dvp_late)
+    const bool dvp_late = IN_LDS && need_betas;
+    if ((need_pose || need_betas) && !dvp_late) lbs_dvp_vertices<IN_LDS>(m, sA, bw.g, tid, wk.dvp + (size_t)h * NV3, nullptr);
     // ---- dA[j][e] = sum_v W[v][j] * [g (x) v_posed | g][e].  The CSR-by-joint list is cut into single-joint
     //      segments of <= 13 entries, one lane each (balanced: the wrist alone owns ~600 entries), then the
     //      segment partials of a joint are summed in index order -- fixed order, bit-reproducible.
@@ -753,6 +778,10 @@ __device__ __forceinline__ void lbs_bwd1_hand(const ihmr_mano& m, const LbsWork&
         for (int sg = m.jseg_start[j]; sg < s1; ++sg) acc += bwd1_part[sg * 12 + e];
         bw.dA[j][e] = acc;
     }
+    // fused tail with a shape gradient: v_posed has been read for the last time (the segment sums above, closed by the barrier), so
+    // d v_posed takes its place in this hand's LDS record -- the shape rows below read it there instead of from the workspace (9.3 KB per
+    // hand written to global memory and read back by the same workgroup).  The finger-pose gradient needs the workspace copy as well
+    if (dvp_late) lbs_dvp_vertices<IN_LDS>(m, sA, bw.g, tid, need_pose ? wk.dvp + (size_t)h * NV3 : nullptr, bw.vp);
     __syncthreads();
 
     // ---- chain backward by tree level
@@ -841,6 +870,31 @@ __device__ __forceinline__ void lbs_bwd1_hand(const ihmr_mano& m, const LbsWork&
             __syncthreads();
         }
         const int wave = tid / WAVE, lane = tid % WAVE;
+        if (IN_LDS) {
+            // d v_posed of this hand is in its LDS record (bw.vp, written by this workgroup's late per-vertex phase several barriers ago):
+            // the 13 basis entries of a row are requested in one batch, the gradients read as they are used.  Per lane the same fmaf
+            // chain in the same order as below
+            for (int l = wave; l < 10; l += LBS_THREADS / WAVE) {
+                float4 srow[NVP / WAVE];
+#pragma unroll
+                for (int t = 0; t < NVP / WAVE; ++t) srow[t] = m.sd4[l * NVP + lane + WAVE * t];  // padding rows are zero
+                __builtin_amdgcn_sched_barrier(0);
+                float acc = 0.f;
+#pragma unroll
+                for (int t = 0; t < NVP / WAVE; ++t) {
+                    const int v = lane + WAVE * t;
+                    if (v < NV) {
+                        acc = __builtin_fmaf(srow[t].x, bw.vp[3 * v], acc);
+                        acc = __builtin_fmaf(srow[t].y, bw.vp[3 * v + 1], acc);
+                        acc = __builtin_fmaf(srow[t].z, bw.vp[3 * v + 2], acc);
+                    }
+                }
+                if (lane < 48) acc = __builtin_fmaf(m.J_shapedirs[lane * 10 + l], bw.dJ[lane / 3][lane % 3], acc);
+                acc = wave_reduce_sum(acc);
+                if (lane == 0) d_betas[h * 10 + l] = acc;
+            }
+            return;
+        }
         // d v_posed of this hand comes back from the workspace (written by this workgroup's per-vertex phase several
         // barriers ago: visible to the whole workgroup); rows and gradients are fetched in two batches of 7 / 6 vertices
         // per lane so that the loads of a batch are in flight together without exceeding the 128-register budget

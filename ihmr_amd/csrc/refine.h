@@ -393,6 +393,15 @@ __global__ __launch_bounds__(384) void opt_adam_skel_kernel(ihmr_mano m, ihmr_op
 // pose offsets, no skinning launch: bit-identical, and slower in both regimes, 52.6 us against 40.0 + 10.3 us per 448 samples and 73.8
 // against 71.1 us per iteration at one batch of 64 -- a thread's four vertices are four dependent gathers of eleven basis rows, where the
 // skinning launch streams each row once for 4 - 8 hands.  docs/experiments.md)
+// What the kernel holds where:
+//   * LDS, static (55 840 B): the loss wave's record (LossShared), the wave sums, and one LbsBwdShared per hand -- the skeleton record `sk` and
+//     `vp` by DMA in phase 0, the output gradients `g` / `gj` written by phase 1; `vp` holds v_posed until the dA segment sums of phase 2 have read
+//     it and, in a stage with a shape gradient, d v_posed after that (lbs_bwd1_hand: dvp_late), which the shape rows read back from LDS.  d v_posed
+//     goes to the workspace only when the finger-pose GEMM needs it;
+//   * LDS, dynamic (2 x nseg x 48 B = 23 808 B at MANO's 248 segments): the per-segment partial sums of dA.  79 648 B in all: two workgroups per CU;
+//   * registers: at most 128 per thread (two workgroups of 512 threads per CU), none spilled -- all three forms are free of scratch and of spilled
+//     scalar registers (tests/test_tail_build_cpu.py), so no launch of the refinement loop uses scratch any more;
+//   * arguments: one record in the kernel-argument segment, of which each phase loads its own fields (TailArgs below).
 // Phase stamps (experiment builds only, -DTAIL_STAMPS; scripts/tail_stamps.py): shader-clock time of each phase of a sample's workgroup,
 // summed per sample and kernel form
 #ifdef TAIL_STAMPS
@@ -403,10 +412,24 @@ __device__ long long g_tail_stamps[3][4096][8];
 #endif
 // dynamic LDS of opt_tail_kernel: [2][nseg][12] floats of the LBS backward
 static inline int opt_tail_dynamic_lds(int nseg) { return 2 * nseg * 12 * (int)sizeof(float); }
+// The launch's arguments are ONE record, and every phase requests the fields it uses from the kernel-argument segment together, at its
+// start (tail_args(): the segment's address passed through an empty asm statement, so that a phase's scalar loads are its own and die
+// with it; by-value copies of the sub-records, of which only the fields the phase reads are loaded).  As eleven by-value
+// arguments -- 904 bytes, ~50 pointers -- the fields that several phases use were loaded once, ahead of phase 1, and stayed live to the
+// end: two of the three forms ran out of scalar registers (46 / 30 of them parked in vector registers) and all three spilled vector
+// registers to scratch.
+struct TailArgs {
+    ihmr_mano m; ihmr_opt_io io; OptWork wk; int B; ihmr_opt_weights w; VertLayout vl; SdfWorkspace ws; int need_cam, need_mask;
+    ParamStep st; int* inside_count;
+};
+__device__ __forceinline__ const TailArgs& tail_args() {
+    typedef const __attribute__((address_space(4))) TailArgs* ArgPtr;      // (the kernel's only explicit argument: offset 0 of the segment)
+    ArgPtr p = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const TailArgs*)p;
+}
 template <bool STEP, bool SKIN = false>
-__global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel(ihmr_mano m, ihmr_opt_io io, OptWork wk, int B, ihmr_opt_weights w,
-                                                                         VertLayout vl, SdfWorkspace ws, int need_cam, int need_mask,
-                                                                         ParamStep st, int* inside_count) {
+__global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel(TailArgs) {
     TL_SCOPE(3 + (STEP ? 1 : 0) + (SKIN ? 1 : 0));
     __shared__ LossShared sh;
     __shared__ float red16[SDF_SAMPLE_THREADS / WAVE];
@@ -422,22 +445,24 @@ __global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel(ihmr_ma
     //      bitmaps here and published them with a workgroup barrier in the middle of phase 1: since round 6 the prep kernel puts the
     //      corner mask of every query into its cell word, and phase 1 has no barrier before the block sum.)
     const int hl = tid / LBS_THREADS;
-    auto dma_backward_inputs = [&]() {
-        if ((need_mask & 7) != 0) {
-            lds_dma_dwords(wk.lbs.v_posed + (size_t)(hl * B + b) * NV3, bw[hl].vp, NV3, tid % LBS_THREADS, LBS_THREADS);
-            lds_dma_dwords(wk.lbs.skel + (size_t)(hl * B + b) * SK_STRIDE, bw[hl].sk, SK_STRIDE, tid % LBS_THREADS, LBS_THREADS);
-        } else if (SKIN) {       // translation stage: the skeleton records stay valid for the next iteration's vertices (phase 3 / 4)
-            lds_dma_dwords(wk.lbs.skel + (size_t)(hl * B + b) * SK_STRIDE, bw[hl].sk, SK_STRIDE, tid % LBS_THREADS, LBS_THREADS);
-        }
-    };
-    dma_backward_inputs();
+    {
+    const TailArgs& a = tail_args();
+    const int B = a.B, need_mask = a.need_mask;
+    const ihmr_opt_io io = a.io; const OptWork wk = a.wk; const ihmr_opt_weights w = a.w; const SdfWorkspace ws = a.ws;     // (by value: the fields
+    const VertLayout vl = a.vl;                                                                  // a phase uses are requested together, at its start)
+    if ((need_mask & 7) != 0) {
+        lds_dma_dwords(wk.lbs.v_posed + (size_t)(hl * B + b) * NV3, bw[hl].vp, NV3, tid % LBS_THREADS, LBS_THREADS);
+        lds_dma_dwords(wk.lbs.skel + (size_t)(hl * B + b) * SK_STRIDE, bw[hl].sk, SK_STRIDE, tid % LBS_THREADS, LBS_THREADS);
+    } else if (SKIN) {       // translation stage: the skeleton records stay valid for the next iteration's vertices (phase 3 / 4)
+        lds_dma_dwords(wk.lbs.skel + (size_t)(hl * B + b) * SK_STRIDE, bw[hl].sk, SK_STRIDE, tid % LBS_THREADS, LBS_THREADS);
+    }
     // ---- phase 1: collision sampling (waves 0-6) + joint / translation / finger losses (wave 7).  Their gradients -- d L / d vertices,
     //      d L / d joints -- are handed to phase 2 through its LDS records, not through global memory (the same values).  One workgroup
     //      barrier inside, at the same place for both kinds of wave: the block sum
     const float mask = (io.hand_type_array[b * 2] + io.hand_type_array[b * 2 + 1]) > 1.5f ? 1.f : 0.f;
     const float gs = w.collision * mask / (ws.loss_div * (float)(io.norm_batch > 0 ? io.norm_batch : B));
     if (tid >= OPT_SAMPLE_WORKERS) {
-        opt_loss_wave(io, wk, B, w, sh, b, tid - OPT_SAMPLE_WORKERS, need_cam, bw);
+        opt_loss_wave(io, wk, B, w, sh, b, tid - OPT_SAMPLE_WORKERS, a.need_cam, bw);
         if (tid == OPT_SAMPLE_WORKERS) red16[OPT_SAMPLE_WORKERS / WAVE] = 0.f;       // (its share of the block sum)
         __syncthreads();
     } else {
@@ -445,20 +470,32 @@ __global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel(ihmr_ma
         // closes optimize(), opt_sample_loss_kernel, writes the ones that are exported)
         sdf_sample_fused(vl, ws, io.loss_batch + 2 * B, B, gs, io.hand_type_array, red16, b, OPT_SAMPLE_WORKERS, bw[0].g, bw[1].g);
     }
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (this wave's DMA writes to LDS have landed; the barrier publishes them)
     __syncthreads();         // the gradients of this sample and the DMA'd records: written above by this workgroup, read below by it
     TAIL_TK(0);
     // ---- phase 2: LBS backward of both hands
-    lbs_bwd1_hand<true>(m, wk.lbs, B, hl * B + b, tid % LBS_THREADS, bw[hl], tail_part + (size_t)hl * m.nseg * 12, nullptr, nullptr,
-                        wk.g_orient, wk.g_shape, wk.g_trans, need_mask, &bw[1]);
+    {
+    const TailArgs& a = tail_args();
+    const ihmr_mano m = a.m; const OptWork wk = a.wk;
+    lbs_bwd1_hand<true, true>(m, wk.lbs, a.B, hl * a.B + b, tid % LBS_THREADS, bw[hl], tail_part + (size_t)hl * m.nseg * 12, nullptr, nullptr,
+                              wk.g_orient, wk.g_shape, wk.g_trans, a.need_mask, &bw[1]);
+    }
     if (!STEP) { TAIL_TK(1); return; }
     __syncthreads();         // the parameter gradients of this sample are in place
     TAIL_TK(1);
     // ---- phase 3: the optimizer step of this iteration, then both skeletons of the next one (threads [0,192) / [192,384))
-    if (b == 0 && tid >= 384 && tid < 384 + SDF_NZERO) sdf_zero_counter(inside_count, tid - 384);   // the next iteration's collision kernels start from zero
-    if (st.mask && tid < OPT_NPARAM) { opt_snapshot_losses(io, B, st, b, tid); opt_param_apply(io, wk, B, st, b, tid); }
+    {
+    const TailArgs& a = tail_args();
+    const ihmr_opt_io io = a.io; const OptWork wk = a.wk; const ParamStep st = a.st;
+    if (b == 0 && tid >= 384 && tid < 384 + SDF_NZERO) sdf_zero_counter(a.inside_count, tid - 384);   // the next iteration's collision kernels start from zero
+    if (st.mask && tid < OPT_NPARAM) { opt_snapshot_losses(io, a.B, st, b, tid); opt_param_apply(io, wk, a.B, st, b, tid); }
+    }
     __syncthreads();         // the updated parameters are read back below by other threads of this workgroup
     TAIL_TK(2);
+    const TailArgs& a = tail_args();
+    const int B = a.B, need_mask = a.need_mask;
+    const ihmr_mano m = a.m; const ihmr_opt_io io = a.io; const OptWork wk = a.wk;
     // (SKIN: the vertex data of phase 4 is requested here, ahead of the skeleton chain: v_posed does not change in such a stage)
     constexpr int VR = (NV + LBS_THREADS - 1) / LBS_THREADS;
     const int lt = tid % LBS_THREADS, hv = hl * B + b;

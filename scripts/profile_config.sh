@@ -10,6 +10,9 @@ export TMPDIR=/tmp
 CMD="python3 bench.py --config $cfg --no-cpu-baseline"
 mkdir -p gpurun_out
 rm -rf gpurun_out/kt gpurun_out/pmc_f gpurun_out/pmc_w gpurun_out/pmc_s
+# every GPU step below runs under its own time limit; the first step that fails or times out ends the script -- nothing more is started on the GPU
+trap 'echo "profile_config: a step ended with status $?: stopping here" >&2' ERR
+set -e
 timeout 400 rocprofv3 --kernel-trace --stats -d gpurun_out/kt -o kt -- $CMD > gpurun_out/${tag}_kt.log 2>&1
 python3 scripts/rocprof_summary.py gpurun_out/kt/kt_results.db gpurun_out/${tag}_kernel_stats.csv | head -12
 timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_f -o f -- $CMD > gpurun_out/${tag}_pmc_f.log 2>&1

@@ -8,6 +8,9 @@ export TMPDIR=/tmp
 CMD="python3 bench.py --steps ${STEPS:-${FUSE:-8}} --warmup ${FUSE:-8} --streams 1 --fuse ${FUSE:-8} --no-cpu-baseline --no-extras --no-work-counters"
 mkdir -p gpurun_out
 rm -rf gpurun_out/kt gpurun_out/pmc_f gpurun_out/pmc_w
+# every GPU step below runs under its own time limit; the first step that fails or times out ends the script -- nothing more is started on the GPU
+trap 'echo "profile_round: a step ended with status $?: stopping here" >&2' ERR
+set -e
 timeout 400 rocprofv3 --kernel-trace --stats -d gpurun_out/kt -o kt -- $CMD > gpurun_out/${tag}_kt.log 2>&1
 python3 scripts/rocprof_summary.py gpurun_out/kt/kt_results.db gpurun_out/${tag}_kernel_stats.csv
 timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_f -o f -- $CMD > gpurun_out/${tag}_pmc_f.log 2>&1
