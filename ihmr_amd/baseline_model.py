@@ -7,7 +7,8 @@ forward (``baseline_model.py:257-282``): encoder (ResNet-50 + IEF head on the ma
 parameters with SEPARATE right / left models, no mirroring (``:208-254``) -> orthographic projection;
 ``test()`` (``:350-355``) adds the collision term for the metric.  The training step (``forward_train`` /
 ``optimize_parameters``, ``src/train_baseline.py:75-80``) is in :mod:`ihmr_amd.baseline_train`, the training-time augmentation
-of its input batches (``BaselineDataset.preprocess_data``) in :mod:`ihmr_amd.augment`; visualisation is out of scope.
+of its input batches (``BaselineDataset.preprocess_data``) in :mod:`ihmr_amd.augment`, ``get_current_visuals`` renders through
+:mod:`ihmr_amd.render`.
 """
 from __future__ import annotations
 
@@ -185,6 +186,11 @@ class InterHandModel(BaselineTrainMixin):
             pred_left_hand_verts=self.pred_left_hand_verts, mano_params_weight=self.mano_params_weight,
             pred_joints_3d=self.pred_joints_3d, gt_joints_3d=self.joints_3d,
             collision_loss_origin_scale=self.collision_loss_origin_scale, do_flip=self.do_flip)
+
+    # baseline_model.py:412-488
+    def get_current_visuals(self, idx=0):
+        from . import render
+        return render.current_visuals(self, idx)
 
     # baseline_model.py:358-375
     def get_pred_result(self):

@@ -15,6 +15,7 @@
 #include "sdf_collision.h"
 #include "preprocess.h"
 #include "augment.h"
+#include "render.h"
 #include "mlp_infer.h"
 #include "refine.h"
 #include "encoder.h"
@@ -1150,6 +1151,40 @@ extern "C" int ihmr_augment_labels(const int32_t* sizes, const ihmr_aug_params* 
     hipLaunchKernelGGL(aug_labels_kernel, dim3(B), dim3(AUG_LABEL_THREADS), 0, (hipStream_t)stream, sizes, params, final_size, joints_2d,
                        joints_3d, mano_pose, mano_betas, mano_params_weight, hand_type_array, out_joints_2d, out_joints_3d, out_mano_pose,
                        out_mano_betas, out_mano_params_weight, out_hand_type_array, out_do_flip, out_hand_trans);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------ visualisation: mesh renderer
+extern "C" size_t ihmr_render_workspace_bytes(int B, int n_verts) {
+    return B > 0 && n_verts > 0 ? sizeof(rnd_vertex) * (size_t)B * (size_t)n_verts : 0;
+}
+
+extern "C" int ihmr_render_meshes(const float* verts, const int32_t* faces, const int32_t* csr_offsets, const int32_t* csr_ids, int n_verts,
+                                  int n_faces, int face_split, const uint8_t* present, const float* albedo, const float* cam,
+                                  const ihmr_render_lights* lights, const uint8_t* background, int S, uint8_t* out_img,
+                                  int32_t* out_face_ids, void* workspace, int B, void* stream) {
+    if (!verts || !faces || !csr_offsets || !csr_ids || !albedo || !cam || !lights || !out_img || !workspace) return -1;
+    if (B <= 0 || B > 65535 || n_verts <= 0 || n_faces <= 0 || n_faces > (1 << 24) || n_verts > (1 << 24) || face_split < 0 ||
+        face_split > n_faces || S < 16 || S > 2048)
+        return -1;
+    if ((uintptr_t)workspace & 3u) return -1;
+    const hipStream_t st = (hipStream_t)stream;
+    rnd_vertex* ws = static_cast<rnd_vertex*>(workspace);
+    hipLaunchKernelGGL(render_vertex_kernel, dim3((n_verts + RND_THREADS - 1) / RND_THREADS, B), dim3(RND_THREADS), 0, st, verts, faces,
+                       csr_offsets, csr_ids, n_verts, n_faces, face_split, albedo, cam, *lights, S, ws);
+    const int tiles = (S + RND_TILE - 1) / RND_TILE;
+    // whole 12-byte runs as three dwords when every run is complete and aligned
+    const int vec = S % RND_PPT == 0 && !((uintptr_t)out_img & 3u) && !((uintptr_t)background & 3u);
+    hipLaunchKernelGGL(render_raster_kernel, dim3(tiles * tiles, B), dim3(RND_THREADS), 0, st, ws, faces, n_verts, n_faces, face_split,
+                       present, background, S, vec, out_img, out_face_ids);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ihmr_draw_keypoints(uint8_t* img, const float* kps, const float* weight, const uint8_t* colour, int B, int S, int K,
+                                   void* stream) {
+    if (!img || !kps || !weight || !colour || B <= 0 || S <= 0 || S > 4096 || K <= 0) return -1;
+    hipLaunchKernelGGL(draw_keypoints_kernel, dim3(B), dim3(RND_KP_THREADS), 0, (hipStream_t)stream, img, kps, weight, (int)colour[0],
+                       (int)colour[1], (int)colour[2], S, K);
     return (int)hipGetLastError();
 }
 

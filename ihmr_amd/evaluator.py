@@ -1,5 +1,7 @@
 """Host-side evaluation, mirroring the metric half of the reference's ``src/utils/evaluator.py`` and
-``src/utils/metric_utils.py`` (CPU / numpy in the reference too; the visualisation half is out of scope).
+``src/utils/metric_utils.py`` (CPU / numpy in the reference too), and its visualisation half (``evaluator.py:184-291``):
+``Evaluator.visualize_result`` renders the stored meshes over their images on the GPU (:mod:`ihmr_amd.render`) and
+``python -m ihmr_amd.evaluator METHOD DATASET`` is the reference's ``main()``.
 
 ``Evaluator.update(data_idxs, pred_results)`` consumes the dict of ``get_pred_result()`` exactly like
 ``evaluator.py:38-97``; the four reported metrics are ``mpjpe_3d``, ``inter_mpjpe_3d``, ``collision_ave``,
@@ -13,6 +15,10 @@ adds them up when the metrics are asked for -- the per-sample Python loop and th
 of ``get_pred_result()`` drop out of a throughput run.
 """
 from __future__ import annotations
+
+import os
+import os.path as osp
+import sys
 
 import numpy as np
 
@@ -58,8 +64,22 @@ def get_single_verts_error(pred_verts, gt_verts, root_weights, scale_factor):
     return (np.linalg.norm(pr - gr, axis=1) / scale_factor).tolist()
 
 
+def load_image_bgr(path):
+    """The default image loader of :meth:`Evaluator.visualize_result`: (H,W,3) uint8 in BGR order, as ``cv2.imread`` returns it."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.ascontiguousarray(np.asarray(im.convert("RGB"))[:, :, ::-1])
+
+
+def write_image_bgr(path, img):
+    """Writes a (H,W,3) uint8 BGR array by the path's extension (stands for ``cv2.imwrite``, evaluator.py:255)."""
+    from PIL import Image
+    Image.fromarray(np.ascontiguousarray(np.asarray(img)[:, :, ::-1])).save(path)
+
+
 class Evaluator:
-    def __init__(self, mano_models=None, data_list=None, image_root=""):
+    def __init__(self, mano_models=None, data_list=None, image_root="", inputSize=224):
+        self.inputSize = inputSize      # evaluator.py:27 (model.inputSize): the visualisation renders at twice this size by default
         self.left_hand_faces = None if mano_models is None else mano_models["left"].faces
         self.right_hand_faces = None if mano_models is None else mano_models["right"].faces
         # wrist row of the joint regressor per hand (MPVPE root), (2,778): 0 = right, 1 = left
@@ -250,3 +270,83 @@ class Evaluator:
     def collision_max(self): return self.metrics_from_sums(self.metric_sums())["collision_max"]
     @property
     def mpvpe_3d(self): return self.metrics_from_sums(self.metric_sums()).get("mpvpe_3d", float("nan"))
+
+    # ------------------------------------------------------------------------------------------ visualisation (evaluator.py:184-275)
+    def _build_dirs(self, res_dir):
+        """evaluator.py:184-190: ``img_name`` = the last four components of ``img_path`` (the last two joined by ``_``)."""
+        for pred in self.pred_results:
+            record = pred["img_path"].split("/")
+            pred["img_name"] = osp.join(*(record[-4:-2] + ["_".join(record[-2:])]))
+            os.makedirs(osp.dirname(osp.join(res_dir, pred["img_name"])) or ".", exist_ok=True)
+
+    def visualize_result(self, res_vis_dir, res_obj_dir, size_type="double", batch_size=64, image_loader=None):
+        """evaluator.py:231-275 for every stored record: the image padded and resized to ``final_size`` (``size_type`` 'double' =
+        2 x inputSize, 'normalized' = inputSize, 'origin' = the image's longer side, which the resize kernel needs to be a multiple
+        of 4), both hands rendered over it for an interacting sample (right ``light_green``, left ``light_blue``) and the one hand of
+        ``hand_type`` otherwise, image stacked over render and written to ``<res_vis_dir>/<img_name>`` as .jpg, the mesh to
+        ``<res_obj_dir>/<img_name>.obj``.  ``image_loader(path) -> (H,W,3) uint8 BGR`` replaces the PIL loader.  The reference forks
+        16 processes of OpenDR; here the records go through the device in batches of ``batch_size``: one resize launch and one render
+        per batch and image size."""
+        import torch
+
+        from . import hip, render, ry_utils
+        from .preprocess import DataProcessor
+        hip.require_gpu()
+        assert size_type in ("origin", "double", "normalized")
+        assert self.right_hand_faces is not None and self.left_hand_faces is not None, "Evaluator needs the MANO models' faces"
+        loader = image_loader or load_image_bgr
+        self._build_dirs(res_vis_dir)
+        self._build_dirs(res_obj_dir)
+        faces = {"right": np.asarray(self.right_hand_faces).astype(np.int64), "left": np.asarray(self.left_hand_faces).astype(np.int64)}
+        nv = hip.NUM_VERTS
+        renderer = render.MeshRenderer(faces["right"], faces["left"], nv, nv)
+        two = np.array([render.COLORS["light_green"], render.COLORS["light_blue"]], np.float32)
+        one = np.array([render.SINGLE_HAND_COLOR, render.SINGLE_HAND_COLOR], np.float32)
+        for start in range(0, len(self.pred_results), batch_size):
+            chunk = self.pred_results[start:start + batch_size]
+            images = [loader(r["img_path"]) for r in chunk]
+            sizes = [int(np.max(im.shape[:2])) if size_type == "origin" else self.inputSize * (2 if size_type == "double" else 1) for im in images]
+            for S in sorted(set(sizes)):
+                rows = [i for i, s in enumerate(sizes) if s == S]
+                img = DataProcessor(final_size=S)([images[i] for i in rows], return_uint8=True)["img_uint8"]
+                zeros = np.zeros((nv, 3), np.float32)
+                hand = lambda r, side: np.asarray(r.get(f"pred_{side}_hand_verts", zeros), np.float32)
+                recs = [chunk[i] for i in rows]
+                inter = [r["hand_type"] == "interacting" for r in recs]
+                present = np.array([[1, 1] if it else [r["hand_type"] == "right", r["hand_type"] == "left"] for r, it in zip(recs, inter)], np.uint8)
+                colors = np.stack([two if it else one for it in inter])
+                up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+                out = renderer.render(up(np.stack([hand(r, "right") for r in recs])), up(np.stack([hand(r, "left") for r in recs])),
+                                      up(np.stack([np.asarray(r["pred_cam_params"], np.float32)[:3] for r in recs])), img,
+                                      present=up(present), colors=up(colors))
+                res = torch.cat([img, out], dim=1).cpu().numpy()               # image over render (evaluator.py:250)
+                for k, r in enumerate(recs):
+                    if inter[k]:                                               # evaluator.py:206-221
+                        verts = np.concatenate((r["pred_right_hand_verts"], r["pred_left_hand_verts"]), axis=0)
+                        f = np.concatenate((faces["right"], faces["left"] + r["pred_right_hand_verts"].shape[0]), axis=0)
+                    else:                                                      # evaluator.py:223-229
+                        verts, f = r[f"pred_{r['hand_type']}_hand_verts"], faces[r["hand_type"]]
+                    write_image_bgr(osp.join(res_vis_dir, r["img_name"]).replace(".png", ".jpg"), res[k])
+                    ry_utils.save_mesh_to_obj(osp.join(res_obj_dir, r["img_name"])[:-4] + ".obj", verts, f)
+
+
+def main():
+    """evaluator.py:278-291: ``python -m ihmr_amd.evaluator METHOD DATASET`` visualises ``evaluate_results/METHOD/DATASET.pkl``."""
+    import shutil
+
+    from . import ry_utils
+    method, dataset = sys.argv[1], sys.argv[2]
+    pkl_path = osp.join("evaluate_results", method, f"{dataset}.pkl")
+    assert osp.exists(pkl_path)
+    evaluator = ry_utils.load_pkl(pkl_path)
+    res_vis_dir = osp.join("evaluate_results", method, dataset, "images")
+    res_obj_dir = osp.join("evaluate_results", method, dataset, "objs")
+    for d in (res_vis_dir, res_obj_dir):                                       # ry_utils.renew_dir
+        if osp.isdir(d):
+            shutil.rmtree(d)
+        os.makedirs(d)
+    evaluator.visualize_result(res_vis_dir, res_obj_dir)
+
+
+if __name__ == "__main__":
+    main()

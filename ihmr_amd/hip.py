@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "ihmr_mlp_workspace_bytes", "ihmr_mlp_stage_head", "ihmr_mlp_forward_select", "ihmr_mlp_camera_select", "ihmr_opt_forward_verts",
     "ihmr_debug_force_lbs_bwd2_streaming", "ihmr_debug_force_full_skin", "ihmr_version", "ihmr_copy_segments", "ihmr_root_align_joints",
     "ihmr_augment_images", "ihmr_augment_labels",
+    "ihmr_render_workspace_bytes", "ihmr_render_meshes", "ihmr_draw_keypoints",
     "ihmr_conv_igemm_bf16", "ihmr_pack_image_bf16", "ihmr_maxpool3x3s2_bf16", "ihmr_avgpool_relu_bf16", "ihmr_cast_f32_bf16",
 ]
 
@@ -130,6 +131,11 @@ class MlpStage(C.Structure):
 
 class TrainWeights(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("joints_2d", "mano_pose", "mano_shape", "hand_trans", "shape_reg", "shape_residual")]
+
+
+class RenderLights(C.Structure):
+    """``ihmr_render_lights``: the three rotated light positions and their colours (float32)."""
+    _fields_ = [("pos", C.c_float * 3 * 3), ("color", C.c_float * 3 * 3)]
 
 
 TIMED_SDF_PREP, TIMED_SDF_DIST, TIMED_OPT_TAIL, TIMED_KERNELS = 0, 1, 2, 4
@@ -300,6 +306,10 @@ def lib():
         L.ihmr_preprocess_images.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp]
         L.ihmr_augment_images.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, i, vp, vp, vp, vp, C.POINTER(C.c_int), vp]
         L.ihmr_augment_labels.argtypes = [vp, vp, i, i] + [vp] * 14 + [vp]
+        L.ihmr_render_workspace_bytes.argtypes = [i, i]
+        L.ihmr_render_workspace_bytes.restype = C.c_size_t
+        L.ihmr_render_meshes.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp, C.POINTER(RenderLights), vp, i, vp, vp, vp, i, vp]
+        L.ihmr_draw_keypoints.argtypes = [vp, vp, vp, C.c_char_p, i, i, i, vp]
         L.ihmr_opt_sdf_stats.argtypes = [vp, vp, C.POINTER(OptIO), i, C.POINTER(OptWeights), vp, vp]
         L.ihmr_opt_sdf_counters.argtypes = [C.POINTER(OptIO), i, vp, i]
         L.ihmr_opt_sdf_inside_bits.argtypes = [C.POINTER(OptIO), i, vp, vp]

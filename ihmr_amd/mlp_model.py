@@ -8,7 +8,7 @@ joint / collision terms (ONE captured launch of the fused kernels that also serv
 ``ihmr_opt_forward_losses``), keep the update per sample only if every filter loss got strictly better-or-equal
 as ``select_better_params`` prescribes (``:592-637``), store to the per-dataset-index "prev" tables
 (``:337-356``).  The training step (``forward / compute_loss / optimize_parameters``, ``src/train_mlp.py:93-99``) is in
-:mod:`ihmr_amd.mlp_train`; ``sync`` (pickle gather) and visualisation are out of scope.
+:mod:`ihmr_amd.mlp_train`, ``get_current_visuals`` renders through :mod:`ihmr_amd.render`; ``sync`` (pickle gather) is out of scope.
 """
 from __future__ import annotations
 
@@ -128,6 +128,7 @@ class MLPModel(MLPTrainMixin):
         self.hand_trans = c["gt_hand_trans"].view(B, 1, 4)
         self.gt_pose_params, self.gt_shape_params, self.mano_params_weight = gp[:, 3:99], gp[:, 99:119], self._in["mano_params_weight"]
         self.data_idxs, self.img_feat = self._in["index"], self._in["img_feat"]
+        self.input_img = input.get("img")         # read by get_current_visuals only (mlp_model.py:162-163)
         self.init_cam, self.init_pose_params, self.init_shape_params, self.init_hand_trans = ip[:, 0:3], ip[:, 3:99], ip[:, 99:119], ip[:, 119:122]
 
     def _stage_inputs(self, keys, input):
@@ -317,6 +318,14 @@ class MLPModel(MLPTrainMixin):
             pred_right_hand_verts=self.pred_right_hand_verts, pred_left_hand_verts=self.pred_left_hand_verts,
             mano_params_weight=self.mano_params_weight, pred_joints_3d=self.pred_joints_3d, gt_joints_3d=gt,
             collision_loss=self.collision_loss_batch, collision_loss_origin_scale=self.collision_loss_origin_scale)
+
+    # mlp_model.py:755-831
+    def get_current_visuals(self, idx=0):
+        from . import render
+        if self.input_img is None:
+            raise ValueError("get_current_visuals needs the batch's 'img' (set_input keeps it when the loader provides it)")
+        self.pred_joints_2d = self._core.buf["joints_2d"]
+        return render.current_visuals(self, idx)
 
     _KEY_ORDER = ("pred_cam_params", "pred_pose_params", "pred_shape_params", "pred_hand_trans", "gt_right_hand_verts", "gt_left_hand_verts",
                   "pred_right_hand_verts", "pred_left_hand_verts", "mano_params_weight", "pred_joints_3d", "gt_joints_3d", "do_flip",

@@ -455,6 +455,34 @@ int ihmr_augment_labels(const int32_t* sizes, const ihmr_aug_params* params, int
                         float* out_mano_betas, float* out_mano_params_weight, float* out_hand_type_array, float* out_do_flip,
                         float* out_hand_trans, void* stream);
 
+/* ------------------------------------------------------------------ visualisation: predicted hand meshes rendered over the image
+ * Stands where the reference hands a scene to OpenDR (an OpenGL / Mesa CPU renderer that is not available to this build):
+ *   utils/render_color_utils.py:27-66,162-198   render_together / render -> SMPLRenderer -> simple_renderer (evaluator.py:206-221)
+ *   utils/vis_util.py:74-88,219-255             render / render_mesh_to_image                 (evaluator.py:223-229)
+ *   utils/vis_util.py:53-71                     draw_keypoints (cv2.circle, radius 3, filled) (baseline_model.py:412-488)
+ * A batched triangle rasteriser: per-vertex Lambertian shading with three point lights, exact integer coverage on a 1/256-pixel
+ * grid with the top-left rule, perspective-correct Gouraud interpolation, a z-buffer held in registers, composite over the image.
+ * The pixel arithmetic is this build's own (csrc/render_pure.h states it; PARITY UNPINNED against OpenDR).
+ * The three light positions, already rotated by Ry(120 degrees) as _rotateY does (float64 on the host, rounded), and their colours: */
+typedef struct ihmr_render_lights { float pos[3][3]; float color[3][3]; } ihmr_render_lights;
+/* bytes of the per-call workspace: one 24-byte record per vertex and sample */
+size_t ihmr_render_workspace_bytes(int B, int n_verts);
+/* verts (B,n_verts,3) float32, model space (the camera translation is applied here);  faces (n_faces,3) int32, the merged table
+ * concat(faces_right, faces_left + 778) of evaluator.py:212-213: faces [0, face_split) belong to hand 0, the rest to hand 1;
+ * csr_offsets (n_verts+1) / csr_ids (3 n_faces) int32: per vertex its incident faces in ascending order (vertex normals are summed in
+ * that order, no atomics);  present (B,2) bytes or NULL (both): a hand whose byte is 0 is not drawn;  albedo (B,2,3) float32 per
+ * sample and hand, channel order of the image (BGR in the reference's tables);  cam (B,3) = [s, tx, ty]: a sample whose s is not a
+ * finite positive number shows its background only;  background (B,S,S,3) bytes or NULL (white);  16 <= S <= 2048;  out_img
+ * (B,S,S,3) bytes;  out_face_ids (B,S,S) int32 or NULL: the visible face per pixel, -1 where none.  Two launches on `stream`, no
+ * allocation, no synchronisation; a face that names a vertex outside [0, n_verts) is skipped.  `lights` is a host pointer. */
+int ihmr_render_meshes(const float* verts, const int32_t* faces, const int32_t* csr_offsets, const int32_t* csr_ids, int n_verts,
+                       int n_faces, int face_split, const uint8_t* present, const float* albedo, const float* cam,
+                       const ihmr_render_lights* lights, const uint8_t* background, int S, uint8_t* out_img, int32_t* out_face_ids,
+                       void* workspace, int B, void* stream);
+/* img (B,S,S,3) bytes, in place;  kps (B,K,2) float32 in [-1,1];  weight (B,K) float32: a keypoint is drawn iff its weight > 0, in
+ * order (a later one overwrites an earlier one), as a filled disc of radius 3 clipped at the border;  colour: 3 bytes (host). */
+int ihmr_draw_keypoints(uint8_t* img, const float* kps, const float* weight, const uint8_t* colour, int B, int S, int K, void* stream);
+
 /* per-kernel timing hook for bench.py -- the ONE piece of mutable PROCESS-GLOBAL state of this library (everything else is stateless
  * apart from the model handle and a per-device cache of the CU count, relaxed atomics: concurrent first calls store the same value): the timer pointer and the pending event pairs are shared by every stream and every thread of the process
  * (a mutex makes concurrent callers safe, it does not separate their measurements); callers that do not set a timer never touch it.
