@@ -187,6 +187,78 @@ IHMR_PURE void sdf_vox_centre(int id, float& x, float& y, float& z) {
     z = (float)(2 * (id >> 10) + 1) / (float)SDF_G - 1.0f;
 }
 
+// ------------------------------------------------------------------------------------- collision: the sampler's arithmetic
+// The cell word of a sampling entry (SdfWorkspace::qcell): SDF_QCELL_IN | (i0 + 1) | (j0 + 1) << 6 | (k0 + 1) << 12 | corner mask << 18 for a
+// query whose cell (i0, j0, k0) in [-1, 31]^3 touches the grid, 0 for any other query.
+#define SDF_QCELL_IN 0x80000000u
+#define SDF_QCELL_MASK_SHIFT 18      // bits 18-25: which of the cell's eight corners are inside voxels (phi holds a distance)
+IHMR_PURE unsigned sdf_qcell_pack(bool in_grid, int i0, int j0, int k0) {
+    return in_grid ? (SDF_QCELL_IN | (unsigned)(i0 + 1) | ((unsigned)(j0 + 1) << 6) | ((unsigned)(k0 + 1) << 12)) : 0u;
+}
+IHMR_PURE void sdf_qcell_cell(unsigned c, int& i0, int& j0, int& k0) {
+    i0 = (int)(c & 63u) - 1; j0 = (int)((c >> 6) & 63u) - 1; k0 = (int)((c >> 12) & 63u) - 1;
+}
+IHMR_PURE unsigned sdf_qcell_with_mask(unsigned c, unsigned m8) { return c | (m8 << SDF_QCELL_MASK_SHIFT); }
+IHMR_PURE unsigned sdf_qcell_mask(unsigned c) { return (c & SDF_QCELL_IN) ? ((c >> SDF_QCELL_MASK_SHIFT) & 0xffu) : 0u; }
+
+// Grid coordinates of the query vertex q against the box (cx, cy, cz, d.b) of the sampled hand, and whether its cell touches the grid at
+// all (false for a query completely outside, and for a non-finite one).  torch's grid_sample: x addresses the fastest axis.
+struct SdfQuery { float ix, iy, iz; bool in_grid; };
+IHMR_PURE SdfQuery sdf_query_cell(float qx, float qy, float qz, float cx, float cy, float cz, const SdfDivisor& d, int swap_xz, int align_corners) {
+    const float nx0 = sdf_div(qx - cx, d), nz0 = sdf_div(qz - cz, d);
+    SdfQuery r;
+    r.ix = sdf_unnorm(swap_xz ? nz0 : nx0, align_corners);
+    r.iy = sdf_unnorm(sdf_div(qy - cy, d), align_corners);
+    r.iz = sdf_unnorm(swap_xz ? nx0 : nz0, align_corners);
+    const float x0 = floorf(r.ix), y0 = floorf(r.iy), z0 = floorf(r.iz);
+    r.in_grid = x0 >= -1.0f && x0 <= (float)(SDF_G - 1) && y0 >= -1.0f && y0 <= (float)(SDF_G - 1) && z0 >= -1.0f && z0 <= (float)(SDF_G - 1);
+    return r;
+}
+
+// Which of a cell's eight corners are inside voxels: w4[c4] is the inside_bits word of column (k0 + (c4 >> 1), j0 + (c4 & 1)), 0 for a
+// column outside the grid; bit 2 c4 of the mask is voxel i0 of that column, bit 2 c4 + 1 voxel i0 + 1.
+IHMR_PURE unsigned sdf_corner_mask(const unsigned* w4, int i0) {
+    unsigned m = 0u;
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) {
+        const unsigned b0 = i0 >= 0 ? ((w4[c4] >> (i0 & 31)) & 1u) : 0u, b1 = i0 + 1 < SDF_G ? ((w4[c4] >> ((i0 + 1) & 31)) & 1u) : 0u;
+        m |= (b0 << (2 * c4)) | (b1 << (2 * c4 + 1));
+    }
+    return m;
+}
+
+// grid_sample(bilinear, zeros padding) at an in-grid (ix, iy, iz) and its gradient with respect to (ix, iy, iz), from the cell's eight
+// corner values pv[di + 2 dj + 4 dk] (a corner outside the grid takes no part, whatever pv holds).  VALUE_ONLY: gx = gy = gz = 0.
+template <bool VALUE_ONLY>
+IHMR_PURE void sdf_trilinear(float ix, float iy, float iz, const float* pv, float& val, float& gx, float& gy, float& gz) {
+    const float x0 = floorf(ix), y0 = floorf(iy), z0 = floorf(iz);
+    const int i0 = (int)x0, j0 = (int)y0, k0 = (int)z0;
+    const float wx1 = ix - x0, wx0 = (x0 + 1.0f) - ix, wy1 = iy - y0, wy0 = (y0 + 1.0f) - iy, wz1 = iz - z0, wz0 = (z0 + 1.0f) - iz;
+    val = gx = gy = gz = 0.f;
+#pragma unroll
+    for (int c8 = 0; c8 < 8; ++c8) {
+        const int di = c8 & 1, dj = (c8 >> 1) & 1, dk = c8 >> 2;
+        const int i = i0 + di, j = j0 + dj, k = k0 + dk;
+        if (i >= 0 && i < SDF_G && j >= 0 && j < SDF_G && k >= 0 && k < SDF_G) {
+            const float p = pv[c8];
+            const float wx = di ? wx1 : wx0, wy = dj ? wy1 : wy0, wz = dk ? wz1 : wz0;
+            val += p * (wx * wy * wz);
+            if (!VALUE_ONLY) {
+                gx += (di ? p : -p) * (wy * wz);
+                gy += (dj ? p : -p) * (wx * wz);
+                gz += (dk ? p : -p) * (wx * wy);
+            }
+        }
+    }
+}
+// ... to the gradient with respect to the query vertex: ix = ((x + 1) G - 1) / 2 (or (x + 1) / 2 (G - 1)), x = (q - c) / s  =>
+// d ix / d q = G / (2 s) (or (G - 1) / (2 s)); with swap_xz back to the vertex's own axes.
+IHMR_PURE void sdf_grad_to_vertex(float& gx, float& gy, float& gz, float sc, int swap_xz, int align_corners) {
+    const float chain = (0.5f * (float)(align_corners ? SDF_G - 1 : SDF_G)) / sc;
+    gx *= chain; gy *= chain; gz *= chain;
+    if (swap_xz) { const float t = gx; gx = gz; gz = t; }
+}
+
 // ------------------------------------------------------------------------------------- MANO: Rodrigues, kinematic chain
 // smplx batch_rodrigues: angle = ||r + 1e-8||, R = I + sin K + (1 - cos) K^2, K = skew(r / angle)
 IHMR_PURE void rodrigues_fwd(const float* r, float* R) {

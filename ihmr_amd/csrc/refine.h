@@ -281,7 +281,7 @@ __global__ __launch_bounds__(SDF_SAMPLE_THREADS) void opt_sample_loss_kernel(ihm
     // (an IHMR-MLP evaluation -- a keep / reject decision follows, no backward -- takes the values from the prep kernel's cell words:
     // the same bits, no gradient; round 6)
     if (sel.mode)
-        sdf_sample_cells(vl, ws, io.loss_batch + 2 * B, io.coll_per_vert, io.coll_origin_scale, B, io.hand_type_array, red16, b, OPT_SAMPLE_WORKERS);
+        sdf_sample_cells(vl, ws, io.loss_batch + 2 * B, B, io.hand_type_array, red16, b, OPT_SAMPLE_WORKERS, SdfEmitValues{io.coll_per_vert, io.coll_origin_scale});
     else
         sdf_sample_block(vl, ws, 0.f, io.loss_batch + 2 * B, io.coll_per_vert, io.coll_origin_scale, nullptr, wk.g_verts, B, gs,
                          io.hand_type_array, red16, b, OPT_SAMPLE_WORKERS);
@@ -468,7 +468,7 @@ __global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel(TailArg
     } else {
         // (inside the loop nobody reads the per-vertex depths: the 12 KB per sample and iteration are not written -- the forward that
         // closes optimize(), opt_sample_loss_kernel, writes the ones that are exported)
-        sdf_sample_fused(vl, ws, io.loss_batch + 2 * B, B, gs, io.hand_type_array, red16, b, OPT_SAMPLE_WORKERS, bw[0].g, bw[1].g);
+        sdf_sample_cells(vl, ws, io.loss_batch + 2 * B, B, io.hand_type_array, red16, b, OPT_SAMPLE_WORKERS, SdfEmitTail{gs, bw[0].g, bw[1].g});
     }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (this wave's DMA writes to LDS have landed; the barrier publishes them)

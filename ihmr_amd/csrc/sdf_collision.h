@@ -120,8 +120,6 @@ struct SdfWorkspace {          // carved from the caller's workspace; H = 2B han
                                //    to grid_sample as it is); 0 (default): phi[z][y][x], the layout grid_sample's (x, y, z) addresses
 };
 
-#define SDF_QCELL_IN 0x80000000u
-#define SDF_QCELL_MASK_SHIFT 18      // bits 18-25 of a cell word: which of the cell's eight corners are inside voxels (phi holds a distance)
 #define SDF_ENT_REFUSED 0x80000000u  // inside_list entry: (hand << 16) | voxel, hand < 32768; 0xffffffff = padding
 #define SDF_MAX_HANDS 32768          // ... so a launch takes at most 16384 samples (every entry point checks: ihmr_hip.hip)
 #define SDF_NCTR 64
@@ -129,6 +127,14 @@ struct SdfWorkspace {          // carved from the caller's workspace; H = 2B han
 #define SDF_NZERO 3                  // counters that have to be zero before the prep kernel: sdf_zero_counter(c, i), i < SDF_NZERO
 __device__ __forceinline__ void sdf_zero_counter(int* c, int i) { c[i < 2 ? i : SDF_CURSOR] = 0; }
 __host__ __device__ inline size_t sdf_xcd_cap(int H) { return (size_t)H * (SDF_NVOX + 64); }   // one batch-wide list
+// the inside_bits words of the four (k, j) columns of a cell (0 for a column outside the grid): w4[c4], c4 = (j - j0) + 2 (k - k0)
+__device__ __forceinline__ void sdf_cell_words(const unsigned* bits, int j0, int k0, unsigned* w4) {
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) {
+        const int j = j0 + (c4 & 1), k = k0 + (c4 >> 1);
+        w4[c4] = (j >= 0 && j < SDF_G && k >= 0 && k < SDF_G) ? bits[k * SDF_G + j] : 0u;
+    }
+}
 
 #define SDF_LCAP_V 1024              // candidate lists per hand (one per inside voxel, in the order of the hand's run at build time)
 #define SDF_LCAP_L 192               // triangles per list (three 64-lane chunks; a voxel whose list would be longer gets none)
@@ -426,18 +432,13 @@ __global__ __launch_bounds__(PT, SDF_PREP_MIN_WAVES) void sdf_prep_kernel(VertLa
             }
         }
         if (!DENSE) {
-            const float qx0 = sdf_div(oq[rep][0] - cx, dsc), qy = sdf_div(oq[rep][1] - cy, dsc), qz0 = sdf_div(oq[rep][2] - cz, dsc);
-            const float qx = ws.swap_xz ? qz0 : qx0, qz = ws.swap_xz ? qx0 : qz0;
-            const float ix = sdf_unnorm(qx, ws.align_corners), iy = sdf_unnorm(qy, ws.align_corners), iz = sdf_unnorm(qz, ws.align_corners);
-            const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
             // completely outside the grid (or non-finite): contributes nothing
-            const bool in_grid = fx >= -1.0f && fx <= (float)(SDF_G - 1) && fy >= -1.0f && fy <= (float)(SDF_G - 1) && fz >= -1.0f &&
-                                 fz <= (float)(SDF_G - 1);
+            const SdfQuery q = sdf_query_cell(oq[rep][0], oq[rep][1], oq[rep][2], cx, cy, cz, dsc, ws.swap_xz, ws.align_corners);
+            const int i0 = (int)floorf(q.ix), j0 = (int)floorf(q.iy), k0 = (int)floorf(q.iz);
             // the query's cell for the fused sampler (entry hnd * 778 + v of sample b): parked in LDS; written to qcell at the end of
             // the kernel together with the inside mask of the cell's eight corners
-            cellw[v] = in_grid ? (SDF_QCELL_IN | (unsigned)((int)fx + 1) | ((unsigned)((int)fy + 1) << 6) | ((unsigned)((int)fz + 1) << 12)) : 0u;
-            if (in_grid) {
-                const int i0 = (int)fx, j0 = (int)fy, k0 = (int)fz;
+            cellw[v] = sdf_qcell_pack(q.in_grid, i0, j0, k0);
+            if (q.in_grid) {
                 unsigned mi = 0;
                 if (i0 >= 0) mi |= 1u << i0;
                 if (i0 + 1 < SDF_G) mi |= 1u << (i0 + 1);
@@ -734,18 +735,13 @@ __global__ __launch_bounds__(PT, SDF_PREP_MIN_WAVES) void sdf_prep_kernel(VertLa
                 const unsigned c = cellw[v];
                 unsigned m = 0u;
                 if (c & SDF_QCELL_IN) {
-                    const int i0 = (int)(c & 63u) - 1, j0 = (int)((c >> 6) & 63u) - 1, k0 = (int)((c >> 12) & 63u) - 1;
-#pragma unroll
-                    for (int c4 = 0; c4 < 4; ++c4) {
-                        const int j = j0 + (c4 & 1), k = k0 + (c4 >> 1);
-                        if (j >= 0 && j < SDF_G && k >= 0 && k < SDF_G) {
-                            const unsigned wbits = parity[k * SDF_G + j];
-                            const unsigned b0 = i0 >= 0 ? ((wbits >> (i0 & 31)) & 1u) : 0u, b1 = i0 + 1 < SDF_G ? ((wbits >> ((i0 + 1) & 31)) & 1u) : 0u;
-                            m |= (b0 << (2 * c4)) | (b1 << (2 * c4 + 1));
-                        }
-                    }
+                    int i0, j0, k0;
+                    unsigned w4[4];
+                    sdf_qcell_cell(c, i0, j0, k0);
+                    sdf_cell_words(parity, j0, k0, w4);
+                    m = sdf_corner_mask(w4, i0);
                 }
-                qc[v] = c | (m << SDF_QCELL_MASK_SHIFT);
+                qc[v] = sdf_qcell_with_mask(c, m);
             }
         }
     }
@@ -1470,19 +1466,62 @@ __global__ __launch_bounds__(SDF_THREADS, 4) void sdf_dist_kernel(SdfWorkspace w
 }
 
 // ------------------------------------------------------------------------------------- sample
-// One workgroup of SDF_SAMPLE_THREADS per sample b; threads tid < nworkers share the 1556 entries.  Entry
-// e = hnd*778 + v samples phi of hand `hnd` at vertex v of hand 1-hnd.
-// Writes per_vert / origin_scale (B,1556), dval (B,1556,3) = d per_vert / d vertex, loss (B)
-// (x mask[b] = [hand_type_array sum > 1.5] when hand_type != nullptr, loss_utils.py:186-188).
-// If gverts != nullptr: fused-path gradient gverts[(1-hnd), b, v, :] = gs * dval  (layout (2,B,778,3)).
+// One workgroup of SDF_SAMPLE_THREADS per sample b; entry e = hnd*778 + v samples phi of hand `hnd` at vertex v of hand 1-hnd.
+// ONE arithmetic core -- sdf_query_cell, sdf_corner_mask, sdf_trilinear, sdf_grad_to_vertex (ihmr_pure.h: host-tested bit for bit) plus
+// the corner loader and the block sum below -- behind two front ends:
+//   sdf_sample_block     starts from the vertices and the hand's inside bitmap (single-shot callers, the training step, the loop's
+//                        separate launches): every value, gradient and robustifier the module offers;
+//   sdf_sample_cells<E>  starts from the prep kernel's cell words (the fused loop): the tail launch's gradients into LDS (SdfEmitTail)
+//                        or the evaluation's values (SdfEmitValues).
+// Same expressions, same order: the same bits from either.
 #define SDF_SAMPLE_THREADS 512
 #define SDF_SAMPLE_NIT 4             // entries per thread: ceil(1556 / 448) with the fused kernel's 448 sampling threads
+
+// The corners of cell (i0, j0, k0) that mask m8 (sdf_corner_mask) names, from the hand's phi into pv[8] (the caller has zeroed it: a
+// voxel outside the mesh is 0 without a load).  The two x-neighbours of a cell are adjacent in memory: one load for the pair when
+// both are wanted (4-byte aligned 8-byte load: the hardware takes dword-aligned global accesses of any width), single loads otherwise.
+__device__ __forceinline__ void sdf_load_corners(const float* __restrict__ phi, int i0, int j0, int k0, unsigned m8, float* pv) {
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) {
+        const int j = j0 + (c4 & 1), k = k0 + (c4 >> 1);
+        const bool b0 = (m8 >> (2 * c4)) & 1u, b1 = (m8 >> (2 * c4 + 1)) & 1u;
+        const float* row = phi + (k * SDF_G + j) * SDF_G;
+        if (b0 && b1) {
+            typedef float sdf_f2u __attribute__((ext_vector_type(2), aligned(4)));
+            const sdf_f2u two = *reinterpret_cast<const sdf_f2u*>(row + i0);
+            pv[2 * c4] = two.x; pv[2 * c4 + 1] = two.y;
+        } else if (b0) {
+            pv[2 * c4] = row[i0];
+        } else if (b1) {
+            pv[2 * c4 + 1] = row[i0 + 1];
+        }
+    }
+}
+
+// loss[b] from the threads' partial sums, in a fixed order: DPP inside each wave, the 16 wave totals through LDS; x mask[b] =
+// [hand_type_array sum > 1.5] when hand_type != nullptr (loss_utils.py:186-188); parent project: sum / num_hands^2
+__device__ __forceinline__ void sdf_block_loss(float acc, float* red16, float* __restrict__ loss, const float* __restrict__ hand_type,
+                                               float loss_div, int b) {
+    const int tid = threadIdx.x;
+    const float wsum = wave_reduce_sum_dpp(acc);
+    if (tid % WAVE == 0) red16[tid / WAVE] = wsum;
+    __syncthreads();
+    if (tid == 0) {
+        float tot = 0.f;
+        for (int wv = 0; wv < SDF_SAMPLE_THREADS / WAVE; ++wv) tot += red16[wv];
+        float mask = 1.0f;
+        if (hand_type) mask = (hand_type[b * 2] + hand_type[b * 2 + 1]) > 1.5f ? 1.f : 0.f;
+        loss[b] = tot / loss_div * mask;
+    }
+}
+
+// Threads tid < nworkers share the 1556 entries.  Writes per_vert / origin_scale (B,1556), dval (B,1556,3) = d per_vert / d vertex, loss (B).
+// If gverts != nullptr: fused-path gradient gverts[(1-hnd), b, v, :] = gs * dval  (layout (2,B,778,3)).
 __device__ __forceinline__ void sdf_sample_block(const VertLayout& vl, const SdfWorkspace& ws, float robustifier,
                                                  float* __restrict__ loss, float* __restrict__ per_vert,
                                                  float* __restrict__ origin, float* __restrict__ dval,
                                                  float* __restrict__ gverts, int B, float gs,
-                                                 const float* __restrict__ hand_type, float* red16, int b, int nworkers,
-                                                 float* g_lds_r = nullptr, float* g_lds_l = nullptr) {
+                                                 const float* __restrict__ hand_type, float* red16, int b, int nworkers) {
     const int tid = threadIdx.x;
     float acc = 0.f;
     // A thread owns the entries tid, tid + nworkers, ... (at most SDF_SAMPLE_NIT).  Three phases over ALL of them, so that the two
@@ -1504,60 +1543,27 @@ __device__ __forceinline__ void sdf_sample_block(const VertLayout& vl, const Sdf
         qv[it][0] = q[0]; qv[it][1] = q[1]; qv[it][2] = q[2];
     }
     __builtin_amdgcn_sched_barrier(0);
-    float pv[SDF_SAMPLE_NIT][8], ixs[SDF_SAMPLE_NIT][3];
+    float pv[SDF_SAMPLE_NIT][8];
+    SdfQuery qc[SDF_SAMPLE_NIT];
     unsigned ibw[SDF_SAMPLE_NIT][4];
-    bool inr[SDF_SAMPLE_NIT];
 #pragma unroll
     for (int it = 0; it < SDF_SAMPLE_NIT; ++it) {
-        const float cx = bx[it].x, cy = bx[it].y, cz = bx[it].z, sc = bx[it].w;
-        const SdfDivisor dsc = sdf_divisor(sc);
-        const float nx0 = sdf_div(qv[it][0] - cx, dsc), nz0 = sdf_div(qv[it][2] - cz, dsc);
-        const float ix = sdf_unnorm(ws.swap_xz ? nz0 : nx0, ws.align_corners), iy = sdf_unnorm(sdf_div(qv[it][1] - cy, dsc), ws.align_corners),
-                    iz = sdf_unnorm(ws.swap_xz ? nx0 : nz0, ws.align_corners);
-        ixs[it][0] = ix; ixs[it][1] = iy; ixs[it][2] = iz;
-        const float x0 = floorf(ix), y0 = floorf(iy), z0 = floorf(iz);
-        inr[it] = on[it] && x0 >= -1.0f && x0 <= (float)(SDF_G - 1) && y0 >= -1.0f && y0 <= (float)(SDF_G - 1) && z0 >= -1.0f &&
-                  z0 <= (float)(SDF_G - 1);
+        qc[it] = sdf_query_cell(qv[it][0], qv[it][1], qv[it][2], bx[it].x, bx[it].y, bx[it].z, sdf_divisor(bx[it].w), ws.swap_xz, ws.align_corners);
+        qc[it].in_grid = qc[it].in_grid && on[it];
 #pragma unroll
         for (int c8 = 0; c8 < 8; ++c8) pv[it][c8] = 0.f;
         ibw[it][0] = ibw[it][1] = ibw[it][2] = ibw[it][3] = 0u;
-        if (inr[it]) {
-            // which of the cell's eight corners hold a distance at all (inside the mesh): one bitmap word per (k, j) row -- a 4 KB table
-            // per hand; most query vertices lie outside the other hand and read nothing else
-            const int j0 = (int)y0, k0 = (int)z0;
-            const unsigned* ib = ws.inside_bits + (size_t)(hn[it] * B + b) * SDF_NCOL;
-#pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4) {
-                const int j = j0 + (c4 & 1), k = k0 + (c4 >> 1);
-                if (j >= 0 && j < SDF_G && k >= 0 && k < SDF_G) ibw[it][c4] = ib[k * SDF_G + j];
-            }
-        }
+        // which of the cell's eight corners hold a distance at all (inside the mesh): one bitmap word per (k, j) row -- a 4 KB table
+        // per hand; most query vertices lie outside the other hand and read nothing else
+        if (qc[it].in_grid)
+            sdf_cell_words(ws.inside_bits + (size_t)(hn[it] * B + b) * SDF_NCOL, (int)floorf(qc[it].iy), (int)floorf(qc[it].iz), ibw[it]);
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int it = 0; it < SDF_SAMPLE_NIT; ++it) {
-        if (inr[it]) {
-            const int i0 = (int)floorf(ixs[it][0]), j0 = (int)floorf(ixs[it][1]), k0 = (int)floorf(ixs[it][2]);
-            const float* phi = ws.phi + (size_t)(hn[it] * B + b) * SDF_NVOX;
-            // the two x-neighbours of a cell are adjacent in memory: one load for the pair when both are inside the grid
-            // (4-byte aligned 8-byte load: the hardware takes dword-aligned global accesses of any width), single loads at
-            // the border of the grid; a voxel outside the mesh is 0 without a load
-#pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4) {
-                const int j = j0 + (c4 & 1), k = k0 + (c4 >> 1);
-                const unsigned wbits = ibw[it][c4];
-                const bool b0 = i0 >= 0 && ((wbits >> (i0 & 31)) & 1u), b1 = i0 + 1 < SDF_G && ((wbits >> ((i0 + 1) & 31)) & 1u);
-                const float* row = phi + (k * SDF_G + j) * SDF_G;
-                if (b0 && b1) {
-                    typedef float sdf_f2u __attribute__((ext_vector_type(2), aligned(4)));
-                    const sdf_f2u two = *reinterpret_cast<const sdf_f2u*>(row + i0);
-                    pv[it][2 * c4] = two.x; pv[it][2 * c4 + 1] = two.y;
-                } else if (b0) {
-                    pv[it][2 * c4] = row[i0];
-                } else if (b1) {
-                    pv[it][2 * c4 + 1] = row[i0 + 1];
-                }
-            }
+        if (qc[it].in_grid) {
+            const int i0 = (int)floorf(qc[it].ix), j0 = (int)floorf(qc[it].iy), k0 = (int)floorf(qc[it].iz);
+            sdf_load_corners(ws.phi + (size_t)(hn[it] * B + b) * SDF_NVOX, i0, j0, k0, sdf_corner_mask(ibw[it], i0), pv[it]);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -1566,31 +1572,9 @@ __device__ __forceinline__ void sdf_sample_block(const VertLayout& vl, const Sdf
         if (!on[it]) continue;
         const int e = tid + it * nworkers, hnd = hn[it], v = vx[it];
         const float sc = bx[it].w;
-        const float ix = ixs[it][0], iy = ixs[it][1], iz = ixs[it][2];
-        const float x0 = floorf(ix), y0 = floorf(iy), z0 = floorf(iz);
         float val = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
-        if (inr[it]) {
-            const int i0 = (int)x0, j0 = (int)y0, k0 = (int)z0;
-            const float fx = ix - x0, fy = iy - y0, fz = iz - z0;
-            const float wx1 = fx, wx0 = (x0 + 1.0f) - ix, wy1 = fy, wy0 = (y0 + 1.0f) - iy, wz1 = fz, wz0 = (z0 + 1.0f) - iz;
-#pragma unroll
-            for (int c8 = 0; c8 < 8; ++c8) {
-                const int di = c8 & 1, dj = (c8 >> 1) & 1, dk = c8 >> 2;
-                const int i = i0 + di, j = j0 + dj, k = k0 + dk;
-                if (i >= 0 && i < SDF_G && j >= 0 && j < SDF_G && k >= 0 && k < SDF_G) {
-                    const float p = pv[it][c8];
-                    const float wx = di ? wx1 : wx0, wy = dj ? wy1 : wy0, wz = dk ? wz1 : wz0;
-                    val += p * (wx * wy * wz);
-                    gx += (di ? p : -p) * (wy * wz);
-                    gy += (dj ? p : -p) * (wx * wz);
-                    gz += (dk ? p : -p) * (wx * wy);
-                }
-            }
-        }
-        // chain: ix = ((x+1)*G - 1)/2 (or (x+1)/2*(G-1)), x = (q - c)/s  =>  d ix / d q = G / (2 s)  (or (G-1) / (2 s))
-        const float chain = (0.5f * (float)(ws.align_corners ? SDF_G - 1 : SDF_G)) / sc;
-        gx *= chain; gy *= chain; gz *= chain;
-        if (ws.swap_xz) { const float t = gx; gx = gz; gz = t; }       // back to the query vertex's own axes
+        if (qc[it].in_grid) sdf_trilinear<false>(qc[it].ix, qc[it].iy, qc[it].iz, pv[it], val, gx, gy, gz);
+        sdf_grad_to_vertex(gx, gy, gz, sc, ws.swap_xz, ws.align_corners);
         if (robustifier > 0.f) {
             const float r = val / robustifier, fr = r * r;
             const float dfr = 2.0f * r / robustifier;       // d fr / d val
@@ -1610,38 +1594,46 @@ __device__ __forceinline__ void sdf_sample_block(const VertLayout& vl, const Sdf
             float* g = gverts + (((size_t)(1 - hnd) * B + b) * NV + v) * 3;
             g[0] = gs * gx; g[1] = gs * gy; g[2] = gs * gz;
         }
-        if (g_lds_r) {     // fused tail: straight into the LBS backward's LDS record of the hand the vertex belongs to (raw hand frame:
-            float* g = (hnd ? g_lds_r : g_lds_l) + 3 * v;       // the left hand's x negated, as lbs_bwd1_hand's staging does)
-            const float g0 = gs * gx;
-            g[0] = hnd ? g0 : -g0; g[1] = gs * gy; g[2] = gs * gz;
-        }
         acc += val;
     }
-    // fixed-order block sum: DPP inside each wave, the 16 wave totals through LDS
-    const float wsum = wave_reduce_sum_dpp(acc);
-    if (tid % WAVE == 0) red16[tid / WAVE] = wsum;
-    __syncthreads();
-    if (tid == 0) {
-        float tot = 0.f;
-        for (int wv = 0; wv < SDF_SAMPLE_THREADS / WAVE; ++wv) tot += red16[wv];
-        float mask = 1.0f;
-        if (hand_type) mask = (hand_type[b * 2] + hand_type[b * 2 + 1]) > 1.5f ? 1.f : 0.f;
-        loss[b] = tot / ws.loss_div * mask;  // parent project: sum / num_hands^2
-    }
+    sdf_block_loss(acc, red16, loss, hand_type, ws.loss_div, b);
 }
 
-// The sampler of the fused tail (opt_tail_kernel): the same values as sdf_sample_block, bit for bit, from what the collision kernels
-// of the iteration have already worked out.
+// The front end of the fused loop: sdf_sample_block's values, bit for bit, from what the collision kernels of the iteration have
+// already worked out.
 //   * the prep kernel stored every query's grid cell (SdfWorkspace::qcell) while forming the needed-voxel mask: the 1556 normalisations
-//     (a third of the old sampler's instructions) are not redone;
-//   * ... and, since round 6, which of the cell's eight corners are inside voxels (bits 18-25 of the cell word: the prep kernel had the
-//     bitmap in LDS when it wrote the word) -- rounds 4-5 staged both hands' 4 KB bitmaps in LDS and needed a workgroup barrier before the
-//     phi values could be requested;
-//   * a query none of whose eight cell corners is an inside voxel -- 94 % of them -- has value 0 and gradient 0: the old code computed
-//     exactly +0 for it (0 * w sums), so it loads nothing more and skips the arithmetic; the others load their
-//     vertex, box and phi values in ONE round trip (the phi addresses follow from the cell word) and run sdf_sample_block's
-//     expressions.  A degenerate hand (box scale outside [1e-6, 1e6]: the oracle's infinities / NaNs) takes the full path for every entry.
+//     (a third of the block sampler's instructions) are not redone;
+//   * ... and which of the cell's eight corners are inside voxels (bits 18-25 of the cell word: the prep kernel had the bitmap in LDS
+//     when it wrote the word): neither the hand's 4 KB bitmap nor a workgroup barrier is needed before the phi values can be requested;
+//   * a query none of whose eight cell corners is an inside voxel -- 94 % of them -- has value 0 and gradient 0: the full arithmetic
+//     computes exactly +0 for it (0 * w sums), so it loads nothing more and skips the arithmetic; the others load their
+//     vertex, box and phi values in ONE round trip (the phi addresses follow from the cell word) and run the core.  A degenerate hand
+//     (box scale outside [1e-6, 1e6]: the oracle's infinities / NaNs) takes the full path for every entry.
 // Two dependent global round trips (cell words, then vertex + phi of the few entries that need them) and no barrier before the block sum.
+// What an entry emits is the policy E's business:
+//   SdfEmitTail    (opt_tail_kernel; every thread of the workgroup takes entries) the gradient, times gs, straight into the LBS
+//                  backward's LDS record of the hand the vertex belongs to -- raw hand frame: the left hand's x negated, as
+//                  lbs_bwd1_hand's staging does;
+//   SdfEmitValues  (opt_sample_loss_kernel for IHMR-MLP's evaluations, which have no backward) per-vertex and origin-scale depth, value
+//                  only.  Called by ALL threads; threads tid >= nworkers (the loss wave) take part in the block sum only.
+struct SdfEmitTail {
+    static constexpr bool GRAD = true, ALL_THREADS = true;
+    float gs;
+    float *g_lds_r, *g_lds_l;
+    __device__ __forceinline__ void operator()(int, int, int hnd, int v, float, float, float gx, float gy, float gz) const {
+        float* g = (hnd ? g_lds_r : g_lds_l) + 3 * v;
+        const float g0 = gs * gx;
+        g[0] = hnd ? g0 : -g0; g[1] = gs * gy; g[2] = gs * gz;
+    }
+};
+struct SdfEmitValues {
+    static constexpr bool GRAD = false, ALL_THREADS = false;
+    float *per_vert, *origin;
+    __device__ __forceinline__ void operator()(int b, int e, int, int, float val, float sc, float, float, float) const {
+        per_vert[(size_t)b * 2 * NV + e] = val;
+        origin[(size_t)b * 2 * NV + e] = val * sc;
+    }
+};
 #ifdef TAIL_STAMPS
 __device__ long long g_samp_stamps[4096][8];
 #define SAMP_TK(k) do { samp_t_[k] = (long long)__builtin_readcyclecounter(); } while (0)
@@ -1650,9 +1642,9 @@ __device__ long long g_samp_stamps[4096][8];
 #define SAMP_TK(k)
 #define SAMP_DRAIN()
 #endif
-__device__ __forceinline__ void sdf_sample_fused(const VertLayout& vl, const SdfWorkspace& ws, float* __restrict__ loss, int B, float gs,
-                                                 const float* __restrict__ hand_type, float* red16, int b, int nworkers,
-                                                 float* g_lds_r, float* g_lds_l) {
+template <class E>
+__device__ __forceinline__ void sdf_sample_cells(const VertLayout& vl, const SdfWorkspace& ws, float* __restrict__ loss, int B,
+                                                 const float* __restrict__ hand_type, float* red16, int b, int nworkers, const E& emit) {
     const int tid = threadIdx.x;
     float acc = 0.f;
 #ifdef TAIL_STAMPS
@@ -1666,7 +1658,7 @@ __device__ __forceinline__ void sdf_sample_fused(const VertLayout& vl, const Sdf
 #pragma unroll
     for (int it = 0; it < SDF_SAMPLE_NIT; ++it) {
         const int e = tid + it * nworkers;
-        on[it] = e < 2 * NV;
+        on[it] = e < 2 * NV && (E::ALL_THREADS || tid < nworkers);
         const int ee = on[it] ? e : 0;
         hn[it] = ee / NV; vx[it] = ee % NV;
         cw[it] = ws.qcell[(size_t)b * 2 * NV + ee];
@@ -1676,28 +1668,23 @@ __device__ __forceinline__ void sdf_sample_fused(const VertLayout& vl, const Sdf
     SAMP_TK(1);
     SAMP_DRAIN();
     SAMP_TK(2);
-    // ---- which of a cell's eight corners hold a distance: bits 18-25 of the cell word (the prep kernel had the bitmap in LDS)
-    const bool fast0 = box0.w >= 1e-6f && box0.w <= 1e6f, fast1 = box1.w >= 1e-6f && box1.w <= 1e6f;
+    // ---- which of a cell's eight corners hold a distance: the mask in the cell word
+    const bool fast0 = sdf_divisor(box0.w).fast, fast1 = sdf_divisor(box1.w).fast;
     unsigned m8[SDF_SAMPLE_NIT];
     bool nz[SDF_SAMPLE_NIT];
 #pragma unroll
     for (int it = 0; it < SDF_SAMPLE_NIT; ++it) {
-        unsigned m = (on[it] && (cw[it] & SDF_QCELL_IN)) ? ((cw[it] >> SDF_QCELL_MASK_SHIFT) & 0xffu) : 0u;
+        unsigned m = on[it] ? sdf_qcell_mask(cw[it]) : 0u;
 #ifdef SDF_QMASK_CHECK      // experiment builds only: the mask recomputed from the hand's bitmap in global memory; mismatches counted, the bitmap's used
         {
             const unsigned c = cw[it];
-            const int i0 = (int)(c & 63u) - 1, j0 = (int)((c >> 6) & 63u) - 1, k0 = (int)((c >> 12) & 63u) - 1;
+            int i0, j0, k0;
+            sdf_qcell_cell(c, i0, j0, k0);
             unsigned mr = 0u;
             if (on[it] && (c & SDF_QCELL_IN)) {
-                const unsigned* ib = ws.inside_bits + (size_t)(hn[it] * B + b) * SDF_NCOL;
-                for (int c4 = 0; c4 < 4; ++c4) {
-                    const int j = j0 + (c4 & 1), k = k0 + (c4 >> 1);
-                    if (j >= 0 && j < SDF_G && k >= 0 && k < SDF_G) {
-                        const unsigned wbits = ib[k * SDF_G + j];
-                        const unsigned b0 = i0 >= 0 ? ((wbits >> (i0 & 31)) & 1u) : 0u, b1 = i0 + 1 < SDF_G ? ((wbits >> ((i0 + 1) & 31)) & 1u) : 0u;
-                        mr |= (b0 << (2 * c4)) | (b1 << (2 * c4 + 1));
-                    }
-                }
+                unsigned w4[4];
+                sdf_cell_words(ws.inside_bits + (size_t)(hn[it] * B + b) * SDF_NCOL, j0, k0, w4);
+                mr = sdf_corner_mask(w4, i0);
             }
             if (mr != m) { atomicAdd(&g_qmask_bad[0], 1u); if (c >> 26 & 31u) atomicAdd(&g_qmask_bad[1], 1u); g_qmask_bad[2] = c; g_qmask_bad[3] = mr; }
             atomicAdd(&g_qmask_bad[4], 1u);
@@ -1718,24 +1705,9 @@ __device__ __forceinline__ void sdf_sample_fused(const VertLayout& vl, const Sdf
         if (nz[it]) {
             const float* q = vl.hand(b, 1 - hn[it]) + 3 * vx[it];
             qv[it][0] = q[0]; qv[it][1] = q[1]; qv[it][2] = q[2];
-            const unsigned c = cw[it];
-            const int i0 = (int)(c & 63u) - 1, j0 = (int)((c >> 6) & 63u) - 1, k0 = (int)((c >> 12) & 63u) - 1;
-            const float* phi = ws.phi + (size_t)(hn[it] * B + b) * SDF_NVOX;
-#pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4) {
-                const int j = j0 + (c4 & 1), k = k0 + (c4 >> 1);
-                const bool b0 = (m8[it] >> (2 * c4)) & 1u, b1 = (m8[it] >> (2 * c4 + 1)) & 1u;
-                const float* row = phi + (k * SDF_G + j) * SDF_G;
-                if (b0 && b1) {
-                    typedef float sdf_f2u __attribute__((ext_vector_type(2), aligned(4)));
-                    const sdf_f2u two = *reinterpret_cast<const sdf_f2u*>(row + i0);
-                    pv[it][2 * c4] = two.x; pv[it][2 * c4 + 1] = two.y;
-                } else if (b0) {
-                    pv[it][2 * c4] = row[i0];
-                } else if (b1) {
-                    pv[it][2 * c4 + 1] = row[i0 + 1];
-                }
-            }
+            int i0, j0, k0;
+            sdf_qcell_cell(cw[it], i0, j0, k0);
+            sdf_load_corners(ws.phi + (size_t)(hn[it] * B + b) * SDF_NVOX, i0, j0, k0, m8[it], pv[it]);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -1744,170 +1716,23 @@ __device__ __forceinline__ void sdf_sample_fused(const VertLayout& vl, const Sdf
 #pragma unroll
     for (int it = 0; it < SDF_SAMPLE_NIT; ++it) {
         if (!on[it]) continue;
-        const int hnd = hn[it], v = vx[it];
+        const float4 bx = hn[it] ? box1 : box0;
+        // (an entry that takes no part: val = +0 and gradient = +0, what the arithmetic gives for eight zero corners and a finite chain)
         float val = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
-        if (nz[it]) {           // sdf_sample_block's expressions, operation for operation
-            const float4 bx = hnd ? box1 : box0;
-            const float cx = bx.x, cy = bx.y, cz = bx.z, sc = bx.w;
-            const SdfDivisor dsc = sdf_divisor(sc);
-            const float nx0 = sdf_div(qv[it][0] - cx, dsc), nz0 = sdf_div(qv[it][2] - cz, dsc);
-            const float ix = sdf_unnorm(ws.swap_xz ? nz0 : nx0, ws.align_corners), iy = sdf_unnorm(sdf_div(qv[it][1] - cy, dsc), ws.align_corners),
-                        iz = sdf_unnorm(ws.swap_xz ? nx0 : nz0, ws.align_corners);
-            const float x0 = floorf(ix), y0 = floorf(iy), z0 = floorf(iz);
-            const bool inr = x0 >= -1.0f && x0 <= (float)(SDF_G - 1) && y0 >= -1.0f && y0 <= (float)(SDF_G - 1) && z0 >= -1.0f && z0 <= (float)(SDF_G - 1);
-            if (inr) {
-                const int i0 = (int)x0, j0 = (int)y0, k0 = (int)z0;
-                const float fx = ix - x0, fy = iy - y0, fz = iz - z0;
-                const float wx1 = fx, wx0 = (x0 + 1.0f) - ix, wy1 = fy, wy0 = (y0 + 1.0f) - iy, wz1 = fz, wz0 = (z0 + 1.0f) - iz;
-#pragma unroll
-                for (int c8 = 0; c8 < 8; ++c8) {
-                    const int di = c8 & 1, dj = (c8 >> 1) & 1, dk = c8 >> 2;
-                    const int i = i0 + di, j = j0 + dj, k = k0 + dk;
-                    if (i >= 0 && i < SDF_G && j >= 0 && j < SDF_G && k >= 0 && k < SDF_G) {
-                        const float p = pv[it][c8];
-                        const float wx = di ? wx1 : wx0, wy = dj ? wy1 : wy0, wz = dk ? wz1 : wz0;
-                        val += p * (wx * wy * wz);
-                        gx += (di ? p : -p) * (wy * wz);
-                        gy += (dj ? p : -p) * (wx * wz);
-                        gz += (dk ? p : -p) * (wx * wy);
-                    }
-                }
-            }
-            const float chain = (0.5f * (float)(ws.align_corners ? SDF_G - 1 : SDF_G)) / sc;
-            gx *= chain; gy *= chain; gz *= chain;
-            if (ws.swap_xz) { const float t = gx; gx = gz; gz = t; }
+        if (nz[it]) {
+            const SdfQuery qc = sdf_query_cell(qv[it][0], qv[it][1], qv[it][2], bx.x, bx.y, bx.z, sdf_divisor(bx.w), ws.swap_xz, ws.align_corners);
+            if (qc.in_grid) sdf_trilinear<!E::GRAD>(qc.ix, qc.iy, qc.iz, pv[it], val, gx, gy, gz);
+            if (E::GRAD) sdf_grad_to_vertex(gx, gy, gz, bx.w, ws.swap_xz, ws.align_corners);
         }
-        // (an entry that takes no part: val = +0 and gradient = +0, what the arithmetic above gives for eight zero corners and a finite chain)
-        float* g = (hnd ? g_lds_r : g_lds_l) + 3 * v;       // raw hand frame: the left hand's x negated, as lbs_bwd1_hand's staging does
-        const float g0 = gs * gx;
-        g[0] = hnd ? g0 : -g0; g[1] = gs * gy; g[2] = gs * gz;
+        emit(b, tid + it * nworkers, hn[it], vx[it], val, bx.w, gx, gy, gz);
         acc += val;
     }
     SAMP_TK(5);
-    // fixed-order block sum: DPP inside each wave, the wave totals through LDS
-    const float wsum = wave_reduce_sum_dpp(acc);
-    if (tid % WAVE == 0) red16[tid / WAVE] = wsum;
-    __syncthreads();
-    if (tid == 0) {
-        float tot = 0.f;
-        for (int wv = 0; wv < SDF_SAMPLE_THREADS / WAVE; ++wv) tot += red16[wv];
-        float mask = 1.0f;
-        if (hand_type) mask = (hand_type[b * 2] + hand_type[b * 2 + 1]) > 1.5f ? 1.f : 0.f;
-        loss[b] = tot / ws.loss_div * mask;  // parent project: sum / num_hands^2
-    }
+    sdf_block_loss(acc, red16, loss, hand_type, ws.loss_div, b);
 #ifdef TAIL_STAMPS
     SAMP_TK(6);
-    if (tid == 0 && b < 4096) { for (int k = 0; k < 6; ++k) g_samp_stamps[b][k] += samp_t_[k + 1] - samp_t_[k]; g_samp_stamps[b][7] += 1; }
+    if (E::ALL_THREADS && tid == 0 && b < 4096) { for (int k = 0; k < 6; ++k) g_samp_stamps[b][k] += samp_t_[k + 1] - samp_t_[k]; g_samp_stamps[b][7] += 1; }
 #endif
-}
-
-// The sampler of IHMR-MLP's evaluations (opt_sample_loss_kernel with a keep / reject decision behind it; round 6): sdf_sample_block's
-// values -- loss, per-vertex depth, origin-scale depth -- from the prep kernel's cell words, as sdf_sample_fused takes them: an entry none
-// of whose eight cell corners is an inside voxel (94 %) is the exact +0 the full arithmetic gives and costs one word; the others load
-// vertex, box and phi in one round trip and run sdf_sample_block's expressions.  No gradient: an evaluation of MLPModel.test() has no
-// backward (the training step and every other caller go through sdf_sample_block).  Called by ALL threads of the workgroup; threads
-// tid >= nworkers (the loss wave) take part in the block sum only.
-__device__ __forceinline__ void sdf_sample_cells(const VertLayout& vl, const SdfWorkspace& ws, float* __restrict__ loss,
-                                                 float* __restrict__ per_vert, float* __restrict__ origin, int B,
-                                                 const float* __restrict__ hand_type, float* red16, int b, int nworkers) {
-    const int tid = threadIdx.x;
-    float acc = 0.f;
-    unsigned cw[SDF_SAMPLE_NIT];
-    bool on[SDF_SAMPLE_NIT];
-    int hn[SDF_SAMPLE_NIT], vx[SDF_SAMPLE_NIT];
-#pragma unroll
-    for (int it = 0; it < SDF_SAMPLE_NIT; ++it) {
-        const int e = tid + it * nworkers;
-        on[it] = e < 2 * NV && tid < nworkers;
-        const int ee = on[it] ? e : 0;
-        hn[it] = ee / NV; vx[it] = ee % NV;
-        cw[it] = ws.qcell[(size_t)b * 2 * NV + ee];
-    }
-    const float4 box0 = *reinterpret_cast<const float4*>(ws.box + (size_t)b * 4), box1 = *reinterpret_cast<const float4*>(ws.box + ((size_t)B + b) * 4);
-    __builtin_amdgcn_sched_barrier(0);
-    const bool fast0 = box0.w >= 1e-6f && box0.w <= 1e6f, fast1 = box1.w >= 1e-6f && box1.w <= 1e6f;
-    unsigned m8[SDF_SAMPLE_NIT];
-    bool nz[SDF_SAMPLE_NIT];
-#pragma unroll
-    for (int it = 0; it < SDF_SAMPLE_NIT; ++it) {
-        const unsigned m = (on[it] && (cw[it] & SDF_QCELL_IN)) ? ((cw[it] >> SDF_QCELL_MASK_SHIFT) & 0xffu) : 0u;
-        m8[it] = m;
-        nz[it] = on[it] && (m != 0u || !(hn[it] ? fast1 : fast0));
-    }
-    float qv[SDF_SAMPLE_NIT][3], pv[SDF_SAMPLE_NIT][8];
-#pragma unroll
-    for (int it = 0; it < SDF_SAMPLE_NIT; ++it) {
-        qv[it][0] = qv[it][1] = qv[it][2] = 0.f;
-#pragma unroll
-        for (int c8 = 0; c8 < 8; ++c8) pv[it][c8] = 0.f;
-        if (nz[it]) {
-            const float* q = vl.hand(b, 1 - hn[it]) + 3 * vx[it];
-            qv[it][0] = q[0]; qv[it][1] = q[1]; qv[it][2] = q[2];
-            const unsigned c = cw[it];
-            const int i0 = (int)(c & 63u) - 1, j0 = (int)((c >> 6) & 63u) - 1, k0 = (int)((c >> 12) & 63u) - 1;
-            const float* phi = ws.phi + (size_t)(hn[it] * B + b) * SDF_NVOX;
-#pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4) {
-                const int j = j0 + (c4 & 1), k = k0 + (c4 >> 1);
-                const bool b0 = (m8[it] >> (2 * c4)) & 1u, b1 = (m8[it] >> (2 * c4 + 1)) & 1u;
-                const float* row = phi + (k * SDF_G + j) * SDF_G;
-                if (b0 && b1) {
-                    typedef float sdf_f2u __attribute__((ext_vector_type(2), aligned(4)));
-                    const sdf_f2u two = *reinterpret_cast<const sdf_f2u*>(row + i0);
-                    pv[it][2 * c4] = two.x; pv[it][2 * c4 + 1] = two.y;
-                } else if (b0) {
-                    pv[it][2 * c4] = row[i0];
-                } else if (b1) {
-                    pv[it][2 * c4 + 1] = row[i0 + 1];
-                }
-            }
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int it = 0; it < SDF_SAMPLE_NIT; ++it) {
-        if (!on[it]) continue;
-        const int e = tid + it * nworkers, hnd = hn[it];
-        const float sc = (hnd ? box1 : box0).w;
-        float val = 0.f;
-        if (nz[it]) {           // sdf_sample_block's expressions, operation for operation (value only)
-            const float4 bx = hnd ? box1 : box0;
-            const SdfDivisor dsc = sdf_divisor(sc);
-            const float nx0 = sdf_div(qv[it][0] - bx.x, dsc), nz0 = sdf_div(qv[it][2] - bx.z, dsc);
-            const float ix = sdf_unnorm(ws.swap_xz ? nz0 : nx0, ws.align_corners), iy = sdf_unnorm(sdf_div(qv[it][1] - bx.y, dsc), ws.align_corners),
-                        iz = sdf_unnorm(ws.swap_xz ? nx0 : nz0, ws.align_corners);
-            const float x0 = floorf(ix), y0 = floorf(iy), z0 = floorf(iz);
-            const bool inr = x0 >= -1.0f && x0 <= (float)(SDF_G - 1) && y0 >= -1.0f && y0 <= (float)(SDF_G - 1) && z0 >= -1.0f && z0 <= (float)(SDF_G - 1);
-            if (inr) {
-                const int i0 = (int)x0, j0 = (int)y0, k0 = (int)z0;
-                const float fx = ix - x0, fy = iy - y0, fz = iz - z0;
-                const float wx1 = fx, wx0 = (x0 + 1.0f) - ix, wy1 = fy, wy0 = (y0 + 1.0f) - iy, wz1 = fz, wz0 = (z0 + 1.0f) - iz;
-#pragma unroll
-                for (int c8 = 0; c8 < 8; ++c8) {
-                    const int di = c8 & 1, dj = (c8 >> 1) & 1, dk = c8 >> 2;
-                    const int i = i0 + di, j = j0 + dj, k = k0 + dk;
-                    if (i >= 0 && i < SDF_G && j >= 0 && j < SDF_G && k >= 0 && k < SDF_G) {
-                        const float wx = di ? wx1 : wx0, wy = dj ? wy1 : wy0, wz = dk ? wz1 : wz0;
-                        val += pv[it][c8] * (wx * wy * wz);
-                    }
-                }
-            }
-        }
-        per_vert[(size_t)b * 2 * NV + e] = val;
-        origin[(size_t)b * 2 * NV + e] = val * sc;
-        acc += val;
-    }
-    // fixed-order block sum: DPP inside each wave, the wave totals through LDS (as sdf_sample_block)
-    const float wsum = wave_reduce_sum_dpp(acc);
-    if (tid % WAVE == 0) red16[tid / WAVE] = wsum;
-    __syncthreads();
-    if (tid == 0) {
-        float tot = 0.f;
-        for (int wv = 0; wv < SDF_SAMPLE_THREADS / WAVE; ++wv) tot += red16[wv];
-        float mask = 1.0f;
-        if (hand_type) mask = (hand_type[b * 2] + hand_type[b * 2 + 1]) > 1.5f ? 1.f : 0.f;
-        loss[b] = tot / ws.loss_div * mask;
-    }
 }
 
 // seam B: grid = B, block = SDF_SAMPLE_THREADS (512)

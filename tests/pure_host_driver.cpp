@@ -132,6 +132,53 @@ int main(int argc, char** argv) {
             out[4 * i + 3] = (float)align_root(r[6]);
         }
         write_out(argv[3], out.data(), out.size() * 4);
+    } else if (!strcmp(op, "qcell")) {              // (in_grid, i0, j0, k0, m8) -> word, unpacked i0, j0, k0, word with the mask, its mask
+        auto in = read_in(argv[2], &n, 5);
+        std::vector<uint32_t> out((size_t)n * 6);
+        for (int i = 0; i < n; ++i) {
+            const float* r = &in[(size_t)i * 5];
+            const unsigned c = sdf_qcell_pack(r[0] != 0.f, (int)r[1], (int)r[2], (int)r[3]);
+            int i0, j0, k0;
+            sdf_qcell_cell(c, i0, j0, k0);
+            const unsigned cm = sdf_qcell_with_mask(c, (unsigned)r[4]);
+            uint32_t* o = &out[(size_t)i * 6];
+            o[0] = c; o[1] = (uint32_t)i0; o[2] = (uint32_t)j0; o[3] = (uint32_t)k0; o[4] = cm; o[5] = sdf_qcell_mask(cm);
+        }
+        write_out(argv[3], out.data(), out.size() * 4);
+    } else if (!strcmp(op, "query")) {              // (q xyz, box centre xyz, scale, swap_xz, align_corners) -> ix, iy, iz bits, in_grid, cell word
+        auto in = read_in(argv[2], &n, 9);
+        std::vector<uint32_t> out((size_t)n * 5);
+        for (int i = 0; i < n; ++i) {
+            const float* r = &in[(size_t)i * 9];
+            const SdfQuery q = sdf_query_cell(r[0], r[1], r[2], r[3], r[4], r[5], sdf_divisor(r[6]), (int)r[7], (int)r[8]);
+            uint32_t* o = &out[(size_t)i * 5];
+            o[0] = bits(q.ix); o[1] = bits(q.iy); o[2] = bits(q.iz); o[3] = q.in_grid ? 1u : 0u;
+            o[4] = q.in_grid ? sdf_qcell_pack(true, (int)floorf(q.ix), (int)floorf(q.iy), (int)floorf(q.iz)) : sdf_qcell_pack(false, 0, 0, 0);
+        }
+        write_out(argv[3], out.data(), out.size() * 4);
+    } else if (!strcmp(op, "trilin")) {             // (in-grid ix, iy, iz, pv[8], scale, swap_xz, align_corners) -> val, d/d(ix, iy, iz), value-only val, d/d vertex
+        auto in = read_in(argv[2], &n, 14);
+        std::vector<float> out((size_t)n * 8);
+        for (int i = 0; i < n; ++i) {
+            const float* r = &in[(size_t)i * 14];
+            float* o = &out[(size_t)i * 8];
+            float z0, z1, z2;
+            sdf_trilinear<false>(r[0], r[1], r[2], r + 3, o[0], o[1], o[2], o[3]);
+            sdf_trilinear<true>(r[0], r[1], r[2], r + 3, o[4], z0, z1, z2);
+            if (z0 != 0.f || z1 != 0.f || z2 != 0.f) { fprintf(stderr, "value-only form returned a gradient\n"); return 3; }
+            o[5] = o[1]; o[6] = o[2]; o[7] = o[3];
+            sdf_grad_to_vertex(o[5], o[6], o[7], r[11], (int)r[12], (int)r[13]);
+        }
+        write_out(argv[3], out.data(), out.size() * 4);
+    } else if (!strcmp(op, "cmask")) {              // (four inside_bits words as bit patterns, i0) -> corner mask
+        auto in = read_in(argv[2], &n, 5);
+        std::vector<uint32_t> out(n);
+        for (int i = 0; i < n; ++i) {
+            uint32_t w[5];
+            memcpy(w, &in[(size_t)i * 5], 20);
+            out[i] = sdf_corner_mask(w, (int)w[4]);
+        }
+        write_out(argv[3], out.data(), out.size() * 4);
     } else {
         fprintf(stderr, "unknown op %s\n", op);
         return 2;

@@ -1377,6 +1377,19 @@ def test_translated_hand_reuse_in_numbers(mano_arrays, finger_arrays, asset, B, 
     assert flips == 0 and vox_diff == 0 and worst <= 5e-6 and worst_abs <= 5e-6, (flips, vox_diff, worst, worst_abs, worst_ulp)
 
 
+def _tail_run_state(m, selected):
+    """What a fused-tail run is compared on: every export, the selections, the optimizer state and the snapshot losses."""
+    return m.get_pred_result(), selected.cpu().numpy(), m.buf["adam_m"].cpu().numpy(), m.buf["snap_loss"].cpu().numpy()
+
+
+def _assert_tail_runs_identical(fused, separate):
+    (a, sa, ma, la), (b, sb, mb, lb) = fused, separate
+    assert np.array_equal(sa, sb) and np.array_equal(ma, mb) and np.array_equal(la, lb)
+    for k in ("pred_cam_params", "pred_pose_params", "pred_shape_params", "pred_hand_trans", "pred_right_hand_verts", "pred_left_hand_verts",
+              "pred_joints_3d", "collision_loss", "collision_loss_origin_scale"):
+        assert np.array_equal(a[k], b[k]), f"{k}: the fused tail launch changed the result"
+
+
 @pytest.mark.parametrize("B,optimizer,overlap", [pytest.param(16, "adam", None, id="16-adam"), pytest.param(64, "adam", None, id="64-adam"),
                                                 pytest.param(9, "sgd", None, id="9-sgd"), pytest.param(64, "adam", "deep", id="deep-64-adam"),
                                                 pytest.param(160, "adam", "deep", id="deep-160-adam")])
@@ -1399,12 +1412,44 @@ def test_fused_tail_launch_does_not_change_a_bit(mano_arrays, B, optimizer, over
         for rep in range(2):
             m.set_input(batch); m.init_optimize(); m.optimize()
             torch.cuda.synchronize()
-        outs.append((m.get_pred_result(), torch.stack(m.selected_history).cpu().numpy(), m.buf["adam_m"].cpu().numpy(), m.buf["snap_loss"].cpu().numpy()))
-    (a, sa, ma, la), (b, sb, mb, lb) = outs
-    assert np.array_equal(sa, sb) and np.array_equal(ma, mb) and np.array_equal(la, lb)
-    for k in ("pred_cam_params", "pred_pose_params", "pred_shape_params", "pred_hand_trans", "pred_right_hand_verts", "pred_left_hand_verts",
-              "pred_joints_3d", "collision_loss", "collision_loss_origin_scale"):
-        assert np.array_equal(a[k], b[k]), f"{k}: the fused tail launch changed the result"
+        outs.append(_tail_run_state(m, torch.stack(m.selected_history)))
+    _assert_tail_runs_identical(*outs)
+
+
+def test_fused_tail_on_a_hand_with_a_degenerate_box_does_not_change_a_bit(mano_arrays):
+    """A hand whose box scale lies outside [1e-6, 1e6] takes the plain division (`sdf_div`), and in the cell-word samplers EVERY entry
+    that samples it runs the full arithmetic, whatever its corner mask says (`nz` set by `!fast`).  The right hand of sample 1 is shrunk
+    towards its centroid: the first shape direction of the right-hand model (which the loop evaluates for both hands) is made
+    `centroid - v_template`, so beta_0 = 1 - 5e-6 leaves an extent of ~1e-6 m (a few dozen float32 ulps at hand coordinates: everything
+    stays finite) -- the hand's other betas are 0 and its finger pose is the rest pose (no pose-blend offsets); every other hand has
+    beta_0 = 0 and is an ordinary hand.  The scale the prep kernel stored is read back and must lie strictly between 0 and 1e-6.  One
+    orientation stage of 3 iterations with the fused tail and with `opt.no_fused_tail`: bit for bit the same."""
+    from ihmr_amd.optimize_model import OptimizeModel
+    B = 2
+    _, batch = _two_hand_verts(mano_arrays, B, 1234)
+    batch = {k: v.clone() for k, v in batch.items()}
+    batch["init_shape_params"][:, [0, 10]] = 0.0
+    batch["init_shape_params"][1, :10] = 0.0
+    batch["init_shape_params"][1, 0] = 1.0 - 5e-6
+    outs = []
+    for off in (False, True):
+        opt = _make_opt(B, epoch=2, save_mid_freq=1)
+        opt.no_fused_tail = off
+        m = OptimizeModel(opt)
+        right = m.mano_models["right"]
+        right.shapedirs[:, :, 0] = right.v_template.mean(dim=0, keepdim=True) - right.v_template      # (in place: re-uploaded by _handle)
+        batch["init_pose_params"][1, 3:48] = -right.hand_mean.cpu()
+        m.set_input(batch); m.init_optimize()
+        m.run_stage(m.strategy[1])
+        torch.cuda.synchronize()
+        _, box = m.sdf_inside_bits()
+        print(f"[parity] degenerate box ({'separate' if off else 'fused'}): scales {box[:, :, 3].tolist()}")
+        assert 0.0 < box[0, 1, 3] < 1e-6 and box[0, 0, 3] >= 1e-6 and (box[1, :, 3] >= 1e-6).all(), box[:, :, 3]
+        assert np.isfinite(m.buf["snap_loss"].cpu().numpy()).all()
+        m.forward_losses()                     # (as optimize() closes: the tail launch does not write the exported per-vertex depths)
+        torch.cuda.synchronize()
+        outs.append(_tail_run_state(m, m.buf["selected"]))
+    _assert_tail_runs_identical(*outs)
 
 
 def test_lbs_bwd2_forms_are_bit_identical(mano_arrays):
