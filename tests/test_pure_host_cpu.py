@@ -160,6 +160,28 @@ def test_rodrigues_forward_and_backward_match_the_oracle(driver):
     assert err < 2e-4, err
 
 
+@pytest.mark.parametrize("scale", [0.0, 1e-6, 1e-4, 1e-3, 1e-2], ids=["zero", "1e-6", "1e-4", "1e-3", "1e-2"])
+def test_rodrigues_backward_near_a_zero_rotation(driver, scale):
+    """The angles the test above leaves out (||r|| <= 1e-2, where the analytic form divides by the angle and `cos a - sin a / a`
+    cancels): no fixed tolerance is right across them, so `rodrigues_bwd` may be 1.5 times as far from the float64 oracle as the oracle's
+    own float32 autograd is, or 2e-5 of the largest gradient -- the criterion of tests/mano_cases.py, which tests/test_gpu_mano_layer.py
+    applies to the kernels at the same angles (with the device's sinf / cosf)."""
+    import mano_cases as MC
+    from oracle.mano_ref import rodrigues_smplx
+    rng = np.random.default_rng(14)
+    n = 2000
+    r = (rng.normal(0, 1, (n, 3)) * scale).astype(np.float32)
+    dR = rng.normal(0, 1, (n, 9)).astype(np.float32)
+    grads = {}
+    for dtype in (torch.float64, torch.float32):
+        rt = torch.tensor(r, dtype=dtype, requires_grad=True)
+        (rodrigues_smplx(rt) * torch.tensor(dR.reshape(n, 3, 3), dtype=dtype)).sum().backward()
+        grads[dtype] = rt.grad.numpy().astype(np.float64)
+    got = driver("rod_bwd", np.concatenate([r, dR], 1))
+    f64 = grads[torch.float64]
+    MC.within(got, f64, grads[torch.float32], MC.floor_of("d_pose", f64), f"rodrigues_bwd on the host, r ~ N(0, {scale:g})")
+
+
 def test_optimizer_steps_are_torch_optim_in_float32(driver):
     rng = np.random.default_rng(5)
     n = 5000
