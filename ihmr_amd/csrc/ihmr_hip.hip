@@ -182,13 +182,16 @@ extern "C" int ihmr_mano_create(const ihmr_mano_arrays* h, ihmr_mano** out) {
         int dev = 0, lds_max = 0;
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
-        const void* tails[3] = {(const void*)opt_tail_kernel<true, true>, (const void*)opt_tail_kernel<true>, (const void*)opt_tail_kernel<false>};
+        // (opt_tail_kernel_trans has no dynamic LDS: it is checked like the others and asks for none)
+        const void* tails[4] = {(const void*)opt_tail_kernel<true, true>, (const void*)opt_tail_kernel<true>, (const void*)opt_tail_kernel<false>,
+                                (const void*)opt_tail_kernel_trans};
         m->tail_fits = 1;
         const int tail_dyn = opt_tail_dynamic_lds(m->nseg);
         for (const void* k : tails) {
             hipFuncAttributes fa;
-            if (hipFuncGetAttributes(&fa, k) != hipSuccess || (long)fa.sharedSizeBytes + tail_dyn > (long)lds_max ||
-                hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, tail_dyn) != hipSuccess)
+            const int dyn_k = k == (const void*)opt_tail_kernel_trans ? 0 : tail_dyn;
+            if (hipFuncGetAttributes(&fa, k) != hipSuccess || (long)fa.sharedSizeBytes + dyn_k > (long)lds_max ||
+                (dyn_k && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, dyn_k) != hipSuccess))
                 m->tail_fits = 0;
         }
         (void)hipGetLastError();
@@ -255,6 +258,13 @@ static void lbs_skin_launch(const ihmr_mano* m, int mode, int N, int B, float* v
 extern "C" int ihmr_debug_force_full_skin(int force) {
     const int prev = g_force_full_skin;
     g_force_full_skin = force ? 1 : 0;
+    return prev;
+}
+// checker switch: ihmr_opt_run_stage launches the three generic forms of opt_tail_kernel only -- no opt_tail_kernel_trans, no kept rotations
+static int g_force_generic_tail = 0;
+extern "C" int ihmr_debug_force_generic_tail(int force) {
+    const int prev = g_force_generic_tail;
+    g_force_generic_tail = force ? 1 : 0;
     return prev;
 }
 
@@ -528,6 +538,14 @@ extern "C" int ihmr_opt_run_stage(const ihmr_mano* m, const ihmr_mano* m_left, c
     if ((pm & IHMR_PB_TRANS) && !(pm & (IHMR_PB_ORIENT_L | IHMR_PB_POSE_L | IHMR_PB_SHAPE_L | IHMR_PB_SHAPE_R)) && io->sdf_no_static_reuse == 0)
         static_mask |= 2 | (2 << 2);
     const bool pose_stage = (need_mask & 2) != 0;
+    // Each stage's tail does only what that stage can move (ihmr_debug_force_generic_tail switches both off):
+    //   * only the translation (and the camera) moves: opt_tail_kernel_trans -- the right hand is left alone, the left hand's vertices are
+    //     the kept pre-shift values plus the new shift;
+    //   * a hand none of whose axis-angles is refined keeps the rotations and the pose feature of its skeleton record in the STEP tails
+    //     (lbs_skel_hand: keep_rot; the record is in LDS whenever the LBS backward runs, need_mask & 7).  opt_default: the shape stage
+    const bool trans_tail = vposed_fixed && need_mask == 8 && !g_force_generic_tail;
+    const int keep_rot = ((need_mask & 7) == 0 || g_force_generic_tail) ? 0
+                         : (((pm & (IHMR_PB_ORIENT_R | IHMR_PB_POSE_R)) ? 0 : 1) | ((pm & (IHMR_PB_ORIENT_L | IHMR_PB_POSE_L)) ? 0 : 2));
     const size_t tail_lds = (size_t)opt_tail_dynamic_lds(m->nseg);
     const int lists_first = sg->keep_lists ? 3 : 2;
     for (int it = 0; it < sg->n_iters; ++it) {
@@ -551,8 +569,10 @@ extern "C" int ihmr_opt_run_stage(const ihmr_mano* m, const ihmr_mano* m_left, c
             hipEvent_t tcur;
             const bool timed = g_timer != nullptr;
             if (timed) { if (int rc2 = timed_begin(&tcur, st)) return rc2; }
-            const TailArgs ta{*m, *io, wk, B, *w, vl, ws, need_cam, need_mask, next, ws.inside_count};
-            if (vposed_fixed && it + 1 < sg->n_iters)
+            const TailArgs ta{*m, *io, wk, B, *w, vl, ws, need_cam, need_mask, next, ws.inside_count, keep_rot, it == 0 ? 1 : 0};
+            if (trans_tail && it + 1 < sg->n_iters)
+                hipLaunchKernelGGL(opt_tail_kernel_trans, dim3(B), dim3(SDF_SAMPLE_THREADS), 0, st, ta);
+            else if (vposed_fixed && it + 1 < sg->n_iters)
                 hipLaunchKernelGGL((opt_tail_kernel<true, true>), dim3(B), dim3(SDF_SAMPLE_THREADS), tail_lds, st, ta);
             else if (!pose_stage && it + 1 < sg->n_iters)
                 hipLaunchKernelGGL(opt_tail_kernel<true>, dim3(B), dim3(SDF_SAMPLE_THREADS), tail_lds, st, ta);

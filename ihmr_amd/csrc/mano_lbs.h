@@ -79,22 +79,26 @@ template <bool TWO_HAND>
 __device__ __forceinline__ void lbs_skel_hand(const ihmr_mano& m, const float* __restrict__ orient,
                                               const float* __restrict__ pose, const float* __restrict__ betas,
                                               const float* __restrict__ trans, int B, float* __restrict__ skel,
-                                              float* __restrict__ joints, float* sk, int h, int tid_in, bool active = true) {
+                                              float* __restrict__ joints, float* sk, int h, int tid_in, bool active = true,
+                                              bool keep_rot = false) {
+    // keep_rot (uniform): no axis-angle of this hand has moved since the record in `sk` was made (a stage that refines neither its
+    // orientation nor its finger pose, from the second iteration on): sPose, the rotations sR and the pose feature already stand in the
+    // record bit for bit -- Rodrigues and the pose-feature rebuild are skipped, everything that depends on the shape or the translation is redone
     const bool left = TWO_HAND && h >= B;
     const int tid = active ? tid_in : (1 << 20);       // an inactive thread fails every range test below
     float* sR = sk + SK_R; float* sJ = sk + SK_J; float* sG = sk + SK_G; float* sA = sk + SK_A;
     const int my_depth = active ? m.depth[tid_in / 12] : -1, my_parent = active ? m.parents[tid_in / 12] : 0;   // kinematic tree: read once, up front
     float* sPF = sk + SK_PF; float* sPose = sk + SK_POSE; float* sBeta = sk + SK_BETA; float* sShift = sk + SK_SHIFT;
-    if (tid < 48) {
+    if (!keep_rot && tid < 48) {
         float v = tid < 3 ? orient[h * 3 + tid] : pose[h * 45 + tid - 3];
         if (left && (tid % 3) != 0) v = -v;  // optimize_model.py:180-188
         sPose[tid] = v + m.pose_mean[tid];
     }
     if (tid >= 64 && tid < 74) sBeta[tid - 64] = betas[h * 10 + tid - 64];
     if (tid >= 128 && tid < 142) sk[SK_SHIFT + tid - 128] = 0.f;  // shift + padding
-    if (tid == 150) sPF[135] = 0.f;
+    if (!keep_rot && tid == 150) sPF[135] = 0.f;
     __syncthreads();
-    if (tid < NJ) rodrigues_fwd(&sPose[3 * tid], &sR[9 * tid]);
+    if (!keep_rot && tid < NJ) rodrigues_fwd(&sPose[3 * tid], &sR[9 * tid]);
     if (tid >= 64 && tid < 64 + 48) {
         const int e = tid - 64;
         float acc = m.J_template[e];
@@ -103,7 +107,7 @@ __device__ __forceinline__ void lbs_skel_hand(const ihmr_mano& m, const float* _
         sJ[e] = acc;
     }
     __syncthreads();
-    if (tid < NPF) {
+    if (!keep_rot && tid < NPF) {
         const int j = 1 + tid / 9, e = tid % 9;
         sPF[tid] = sR[9 * j + e] - ((e == 0 || e == 4 || e == 8) ? 1.0f : 0.0f);
     }

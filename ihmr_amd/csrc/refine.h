@@ -21,6 +21,7 @@ struct OptWork {  // carved from ihmr_opt_io.workspace
     float* g_pose;      // (2,B,45)
     float* g_shape;     // (2,B,10)
     float* g_trans;     // (B,3)
+    float* kept_left;   // (B,778,3)  translation stage: the left hand's skinned vertices before the shift, x negated (opt_tail_kernel_trans)
     void* sdf_ws;
 };
 
@@ -30,6 +31,7 @@ static inline size_t opt_ws_bytes(int B) {
     n += lbs_ws_bytes(2 * B);
     n += (size_t)B * 42 * 3 * 4 * 2;      // joints_raw, g_joints
     n += (size_t)B * (3 + 6 + 90 + 20 + 3 + 3 + 1) * 4;
+    n += (size_t)B * NV3 * 4 + 256;       // kept_left
     n = (n + 255) & ~(size_t)255;
     n += 8192;
     return n + sdf_ws_bytes(2 * B, true);
@@ -49,6 +51,7 @@ static inline OptWork opt_carve(void* ws, int B) {
     w.g_shape = (float*)take((size_t)B * 20 * 4);
     w.g_trans = (float*)take((size_t)B * 3 * 4);
     w.g_cam = (float*)take((size_t)B * 3 * 4);
+    w.kept_left = (float*)take((size_t)B * NV3 * 4);
     w.sdf_ws = (void*)p;
     return w;
 }
@@ -72,8 +75,10 @@ struct LossShared {
 
 // gj_lds (fused tail): the joint gradients go straight to the LBS backward's LDS records -- bw[hand].gj, raw hand frame: x of the left
 // hand negated, what lbs_bwd1_hand's staging does with the values it reads back from global memory -- instead of wk.g_joints
+// (GJ: any record with a `float gj[21][3]` per hand -- LbsBwdShared, or the translation tail's TransTailHand)
+template <class GJ = LbsBwdShared>
 __device__ __forceinline__ void opt_loss_wave(const ihmr_opt_io& io, const OptWork& wk, int B, const ihmr_opt_weights& w,
-                                              LossShared& sh, int b, int j, int need_cam, LbsBwdShared* gj_lds = nullptr) {
+                                              LossShared& sh, int b, int j, int need_cam, GJ* gj_lds = nullptr) {
     const bool act = j < 42;
     const int Bn = io.norm_batch > 0 ? io.norm_batch : B;   // the batch the reference's means run over
     // ---- every global input of this sample first, in one batch (the stores below may alias them as far as the
@@ -389,6 +394,10 @@ __global__ __launch_bounds__(384) void opt_adam_skel_kernel(ihmr_mano m, ihmr_op
 // SKIN (with STEP, stages that keep v_posed -- neither finger pose nor shape moves): a fourth phase skins the stored v_posed of both
 // hands with the skeletons just computed (= lbs_skin_kernel<true, REUSE>, the same operations in the same order: the same bits), so
 // the next iteration starts at the collision kernels: 3 launches per iteration.
+// Each stage's tail does only what the stage can move: a stage that moves ONLY the translation (need_mask == 8) runs opt_tail_kernel_trans
+// below instead of the <true, true> form (no second skinning of hands whose pre-shift vertices cannot change), and in the STEP phase a hand
+// none of whose axis-angles the stage refines keeps the rotations and the pose feature of its skeleton record (TailArgs::keep_rot:
+// the shape stage); ihmr_debug_force_generic_tail switches both off -- the same bits either way (tests/test_gpu_stage_tails.py).
 // (Round 6 tried a third form for the shape stage -- the fourth phase rebuilding v_posed = (v_template + shapedirs . beta) + P from the stored
 // pose offsets, no skinning launch: bit-identical, and slower in both regimes, 52.6 us against 40.0 + 10.3 us per 448 samples and 73.8
 // against 71.1 us per iteration at one batch of 64 -- a thread's four vertices are four dependent gathers of eleven basis rows, where the
@@ -421,6 +430,8 @@ static inline int opt_tail_dynamic_lds(int nseg) { return 2 * nseg * 12 * (int)s
 struct TailArgs {
     ihmr_mano m; ihmr_opt_io io; OptWork wk; int B; ihmr_opt_weights w; VertLayout vl; SdfWorkspace ws; int need_cam, need_mask;
     ParamStep st; int* inside_count;
+    int keep_rot;      // bit 0 / 1: no axis-angle of the right / left hand moves in this stage -- lbs_skel_hand keeps the record's rotations
+    int fill_kept;     // opt_tail_kernel_trans: this launch computes OptWork::kept_left (the stage's first STEP launch)
 };
 __device__ __forceinline__ const TailArgs& tail_args() {
     typedef const __attribute__((address_space(4))) TailArgs* ArgPtr;      // (the kernel's only explicit argument: offset 0 of the segment)
@@ -537,8 +548,9 @@ __global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel(TailArg
         }
     } else {
         const int hs = tid / 192;
+        // (keep_rot: a hand none of whose axis-angles the stage refines keeps sR / the pose feature of the record phase 0 brought in)
         lbs_skel_hand<true>(m, io.orient, io.pose, io.shape, io.trans, B, wk.lbs.skel, wk.joints_raw, bw[hs < 2 ? hs : 0].sk, (hs < 2 ? hs : 0) * B + b, tid % 192,
-                            hs < 2);
+                            hs < 2, ((a.keep_rot >> (hs < 2 ? hs : 0)) & 1) != 0);
     }
     TAIL_TK(3);
     if (!SKIN) return;
@@ -592,6 +604,173 @@ __global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel(TailArg
             }
     }
     TAIL_TK(4);
+}
+
+// The tail of a stage that moves ONLY the translation (and possibly the camera): need_mask == 8 with v_posed kept, every iteration but
+// the stage's last.  The generic <true, true> form spends its last phase skinning both hands again although nothing this stage can
+// move reaches the result:
+//   * the right hand does not move at all -- its vertices, fingertip joints and skeleton record stay what the stage's first iteration made;
+//   * the left hand only translates: its skinned vertex before the shift, T . v_posed + T3 with x negated, is the same bits in every
+//     iteration; what changes is the one addition of the shift per coordinate.
+// So the stage's first STEP launch (TailArgs::fill_kept) skins the left hand exactly as the generic phase 4 does and stores the value
+// BEFORE the shift is added (OptWork::kept_left), and every launch writes verts = kept + shift: the generic form's last operation on the
+// same operands, hence the same bits.  Phases 1-3 are the generic form's device functions and expressions; of the LBS backward only the
+// left-hand gradient sum (= d L / d shift, lbs_bwd1_hand's first block: lane partials in r order, DPP wave sums, the four wave totals in
+// index order) is left.  No v_posed, no right-hand record, no dynamic LDS: ~27 KB of static LDS, and the registers of the sampler.
+struct TransTailHand { float g[NV3]; float gj[21][3]; };      // what phase 1 writes per hand (raw hand frame)
+__global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel_trans(TailArgs) {
+    TL_SCOPE(5);
+    __shared__ LossShared sh;
+    __shared__ float red16[SDF_SAMPLE_THREADS / WAVE];
+    __shared__ TransTailHand th[2];
+    __shared__ __attribute__((aligned(16))) float skl[SK_STRIDE];      // the left hand's skeleton record
+    __shared__ float wsum[LBS_THREADS / WAVE][4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    // ---- phase 0: the left hand's skeleton record by DMA (its wrist, posed joints and skinning matrices); it lands while phase 1 runs
+    {
+    const TailArgs& a = tail_args();
+    const int B = a.B;
+    const ihmr_opt_io io = a.io; const OptWork wk = a.wk; const ihmr_opt_weights w = a.w; const SdfWorkspace ws = a.ws;
+    const VertLayout vl = a.vl;
+    lds_dma_dwords(wk.lbs.skel + ((size_t)B + b) * SK_STRIDE, skl, SK_STRIDE, tid, SDF_SAMPLE_THREADS);
+    // ---- phase 1: collision sampling + losses, as opt_tail_kernel
+    const float mask = (io.hand_type_array[b * 2] + io.hand_type_array[b * 2 + 1]) > 1.5f ? 1.f : 0.f;
+    const float gs = w.collision * mask / (ws.loss_div * (float)(io.norm_batch > 0 ? io.norm_batch : B));
+    if (tid >= OPT_SAMPLE_WORKERS) {
+        opt_loss_wave(io, wk, B, w, sh, b, tid - OPT_SAMPLE_WORKERS, a.need_cam, th);
+        if (tid == OPT_SAMPLE_WORKERS) red16[OPT_SAMPLE_WORKERS / WAVE] = 0.f;
+        __syncthreads();
+    } else {
+        sdf_sample_cells(vl, ws, io.loss_batch + 2 * B, B, io.hand_type_array, red16, b, OPT_SAMPLE_WORKERS, SdfEmitTail{gs, th[0].g, th[1].g});
+    }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    // ---- phase 2: d L / d shift = sum over the left hand's vertex and joint gradients (threads [0,256), lbs_bwd1_hand's order)
+    constexpr int VR = (NV + LBS_THREADS - 1) / LBS_THREADS;
+    if (tid < LBS_THREADS) {
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int r = 0; r < VR; ++r) {
+            const int v = tid + r * LBS_THREADS;
+            s0 += v < NV ? -th[1].g[3 * v] : 0.f;            // (x stored negated: negated back, exactly)
+            s1 += v < NV ? th[1].g[3 * v + 1] : 0.f;
+            s2 += v < NV ? th[1].g[3 * v + 2] : 0.f;
+        }
+        float gjl[3] = {0.f, 0.f, 0.f};
+        if (tid < 21) { gjl[0] = -th[1].gj[tid][0]; gjl[1] = th[1].gj[tid][1]; gjl[2] = th[1].gj[tid][2]; }
+        s0 += gjl[0]; s1 += gjl[1]; s2 += gjl[2];
+        s0 = wave_reduce_sum_dpp(s0); s1 = wave_reduce_sum_dpp(s1); s2 = wave_reduce_sum_dpp(s2);
+        if (tid % WAVE == 0) { wsum[tid / WAVE][0] = s0; wsum[tid / WAVE][1] = s1; wsum[tid / WAVE][2] = s2; }
+    }
+    __syncthreads();
+    if (tid < 3) {
+        float t = 0.f;
+#pragma unroll
+        for (int wv = 0; wv < LBS_THREADS / WAVE; ++wv) t += wsum[wv][tid];
+        tail_args().wk.g_trans[b * 3 + tid] = t;
+    }
+    __syncthreads();         // the translation gradient of this sample is in place
+    // ---- phase 3: the optimizer step of this iteration; the kept vertices of phase 4 are requested ahead of it
+    constexpr int ER = (NV3 + SDF_SAMPLE_THREADS - 1) / SDF_SAMPLE_THREADS;
+    float kept[ER], kept_tip = 0.f;
+#pragma unroll
+    for (int r = 0; r < ER; ++r) kept[r] = 0.f;
+    {
+    const TailArgs& a = tail_args();
+    const ihmr_opt_io io = a.io; const OptWork wk = a.wk; const ParamStep st = a.st;
+    if (!a.fill_kept) {
+#pragma unroll
+        for (int r = 0; r < ER; ++r) kept[r] = wk.kept_left[(size_t)b * NV3 + min(tid + r * SDF_SAMPLE_THREADS, NV3 - 1)];
+        if (tid < IHMR_NUM_TIPS * 3) kept_tip = wk.kept_left[(size_t)b * NV3 + 3 * a.m.tip_ids[tid / 3] + tid % 3];
+    }
+    if (b == 0 && tid >= 384 && tid < 384 + SDF_NZERO) sdf_zero_counter(a.inside_count, tid - 384);
+    if (st.mask && tid < OPT_NPARAM) { opt_snapshot_losses(io, a.B, st, b, tid); opt_param_apply(io, wk, a.B, st, b, tid); }
+    }
+    __syncthreads();         // the updated parameters are read back below by other threads of this workgroup
+    const TailArgs& a = tail_args();
+    const int B = a.B;
+    const ihmr_mano m = a.m; const ihmr_opt_io io = a.io; const OptWork wk = a.wk;
+    // the left hand's shift (= hand_trans + right wrist - mirrored left wrist) with lbs_skel_hand's own expression, and its posed joints
+    if (tid < 3) {
+        const float* br = io.shape + (size_t)b * 10;                 // right wrist: J_template[0] + J_shapedirs[0] . beta_right
+        float jr = m.J_template[tid];
+#pragma unroll
+        for (int l = 0; l < 10; ++l) jr = __builtin_fmaf(m.J_shapedirs[tid * 10 + l], br[l], jr);
+        const float* sJl = skl + SK_J;
+        const float jl = tid == 0 ? -sJl[0] : sJl[tid];              // mirrored left wrist
+        const float sh = io.trans[b * 3 + tid] + (jr - jl);
+        skl[SK_SHIFT + tid] = sh;
+        wk.lbs.skel[((size_t)B + b) * SK_STRIDE + SK_SHIFT + tid] = sh;
+    }
+    __syncthreads();
+    if (tid < NJ * 3) {
+        const int j = tid / 3, k = tid % 3;
+        const float val = skl[SK_G + 12 * j + 4 * k + 3];
+        wk.joints_raw[((size_t)b * 42 + 21 + j) * 3 + k] = (k == 0 ? -val : val) + skl[SK_SHIFT + k];
+    }
+    // ---- phase 4: the next iteration's left-hand vertices = kept + shift (the right hand's stay)
+    const float* sShift = skl + SK_SHIFT;
+    float* dstv = io.verts + ((size_t)B + b) * NV3;
+    if (a.fill_kept) {
+        // the generic form's phase 4 for the left hand (= lbs_skin_kernel<true, REUSE>), by all 512 threads; the value before the shift is kept
+        const float* sA = skl + SK_A;
+#pragma unroll 1
+        for (int v = tid; v < NV; v += SDF_SAMPLE_THREADS) {      // (once per stage: kept small, not fast)
+            const float* s0 = wk.lbs.v_posed + ((size_t)(B + b) * NV + v) * 3;
+            const float vp[3] = {s0[0], s0[1], s0[2]};
+            float T[12];
+#pragma unroll
+            for (int e = 0; e < 12; ++e) T[e] = 0.f;
+            if (m.sparse4) {
+                const float4 wr = m.w4_w[v];
+                const uint32_t jr = m.w4_j[v];
+                const float wv[4] = {wr.x, wr.y, wr.z, wr.w};
+#pragma unroll
+                for (int sI = 0; sI < 4; ++sI) {
+                    const float4* A4 = reinterpret_cast<const float4*>(sA + 12 * (int)((jr >> (8 * sI)) & 0xffu));
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) {
+                        const float4 a4 = A4[q];
+                        T[4 * q] = __builtin_fmaf(wv[sI], a4.x, T[4 * q]);
+                        T[4 * q + 1] = __builtin_fmaf(wv[sI], a4.y, T[4 * q + 1]);
+                        T[4 * q + 2] = __builtin_fmaf(wv[sI], a4.z, T[4 * q + 2]);
+                        T[4 * q + 3] = __builtin_fmaf(wv[sI], a4.w, T[4 * q + 3]);
+                    }
+                }
+            } else {
+#pragma unroll 1
+                for (int j = 0; j < NJ; ++j) {
+                    const float wj = m.weights[v * NJ + j];
+#pragma unroll
+                    for (int e = 0; e < 12; ++e) T[e] = __builtin_fmaf(wj, sA[12 * j + e], T[e]);
+                }
+            }
+            float out[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) out[q] = T[4 * q + 0] * vp[0] + T[4 * q + 1] * vp[1] + T[4 * q + 2] * vp[2] + T[4 * q + 3];
+            out[0] = -out[0];
+            float* kd = wk.kept_left + (size_t)b * NV3 + 3 * v;
+            kd[0] = out[0]; kd[1] = out[1]; kd[2] = out[2];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) out[q] = out[q] + sShift[q];
+            dstv[3 * v] = out[0]; dstv[3 * v + 1] = out[1]; dstv[3 * v + 2] = out[2];
+#pragma unroll
+            for (int t = 0; t < IHMR_NUM_TIPS; ++t)
+                if (v == m.tip_ids[t]) {  // fingertip joints are vertices
+                    float* jd = wk.joints_raw + ((size_t)b * 42 + 21 + NJ + t) * 3;
+                    jd[0] = out[0]; jd[1] = out[1]; jd[2] = out[2];
+                }
+        }
+        return;
+    }
+#pragma unroll
+    for (int r = 0; r < ER; ++r) {
+        const int i = tid + r * SDF_SAMPLE_THREADS;
+        if (i < NV3) dstv[i] = kept[r] + sShift[i % 3];
+    }
+    if (tid < IHMR_NUM_TIPS * 3)    // fingertip joints are vertices: the same sum on the same operands
+        wk.joints_raw[((size_t)b * 42 + 21 + NJ + tid / 3) * 3 + tid % 3] = kept_tip + sShift[tid % 3];
 }
 
 // IHMR-MLP, a stage that moves ONLY the camera (mlp_default's last: `pred_cam_params`, filter and select on joints_2d_loss_p;

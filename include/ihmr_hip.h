@@ -565,6 +565,11 @@ int ihmr_debug_force_lbs_bwd2_streaming(int force);
  * moves the shape but not the finger pose stores the pose-blend offsets in its first iteration and reuses them after: no pose rows read).
  * The two produce the same bits (tests/test_gpu_parity.py::test_skin_keeps_pose_offsets_bit_identically).  Returns the previous value. */
 int ihmr_debug_force_full_skin(int force);
+/* checker switch (tests only): force = 1 makes ihmr_opt_run_stage launch only the generic forms of its tail kernel; 0 restores the default
+ * (a stage that moves only the translation runs the tail that keeps the right hand and shifts the left hand's stored vertices, and a
+ * hand whose axis-angles the stage does not refine keeps the rotations of its skeleton record).  The two produce the same bits
+ * (tests/test_gpu_stage_tails.py).  Returns the previous value. */
+int ihmr_debug_force_generic_tail(int force);
 
 const char* ihmr_version(void);
 

@@ -7,7 +7,7 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ("sdf_dist_kernel", "sdf_prep_kernel", "opt_tail_kernel<true, true>", "opt_tail_kernel<true, false>", "opt_tail_kernel<false, false>",
+KERNELS = ("sdf_dist_kernel", "sdf_prep_kernel", "opt_tail_kernel_trans", "opt_tail_kernel<true, true>", "opt_tail_kernel<true, false>", "opt_tail_kernel<false, false>",
            "lbs_skin_kernel<true, 0", "lbs_skin_kernel<true, 2")
 LABEL = {"f7": "7 batches = 448 samples: the driver's `--steps 20` run (three sequences of 7 + 7 + 6)", "f8": "8 batches = 512 samples",
          "f1": "one batch of 64 (the latency case)"}

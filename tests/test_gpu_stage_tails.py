@@ -1,0 +1,168 @@
+"""Each stage's tail does only what the stage can move -- against the generic tail forms and against the separate launches, bit for bit.
+
+* A stage that moves only the translation (and possibly the camera) runs `opt_tail_kernel_trans`: the right hand is not skinned again,
+  the left hand's next vertices are the kept pre-shift values plus the new shift (`OptWork::kept_left`, filled by the stage's first
+  STEP launch).
+* A hand none of whose axis-angles the stage refines keeps the rotations and the pose feature of its skeleton record in the STEP tails.
+
+`ihmr_debug_force_generic_tail(1)` launches the generic forms only, `opt.no_fused_tail` runs the separate launches the tail
+replaces.  Every comparison is
+`np.array_equal` on `uint32` views: every array of `get_pred_result()`, the parameter blocks, the optimizer state, the snapshot
+losses and parameters, the selection and the vertex buffer.
+
+The translated-hand reuse of the collision grid (`sdf_no_static_reuse` = 0) is an acceleration of its own; the three runs of a case
+share its setting.  The translation cases run a second pair -- the new tail against the separate launches -- with the reuse switched
+off (`opt.sdf_no_translated_reuse`, `sdf_no_static_reuse` = 2), so the tail is checked with the left hand's grid kept and rebuilt."""
+import types
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+STATE_KEYS = ("cam", "trans", "orient", "pose", "shape", "adam_m", "adam_v", "snap_loss", "snap_params", "selected", "verts", "joints_3d",
+              "joints_2d", "loss_batch")
+
+
+def _make_opt(B, epoch, freq, **extra):
+    return types.SimpleNamespace(isTrain=False, dist=False, process_rank=-1, batchSize=B, inputSize=224, num_joints=42,
+                                 total_params_dim=122, cam_params_dim=3, pose_params_dim=96, shape_params_dim=20,
+                                 trans_params_dim=3, model_root="", strategy="opt_default", save_mid_freq=freq,
+                                 optimizer="adam", opt_epoch=epoch, **extra)
+
+
+_BATCHES = {}
+
+
+def _batch(mano_arrays, kind, B):
+    """default: the synthetic batch (B = 3: control / right hand only / left hand only -- a (1, 0) sample, collision gradient scale 0);
+    deep: the deep-overlap hands of the deep-interpenetration tests; far: the default batch with the left hands moved a metre away
+    (no collision: only the fingertip gradients are non-zero).  Built once, handed out unchanged."""
+    key = (kind, B)
+    if key not in _BATCHES:
+        from helpers import DEEP_SEED, oracle_two_hand_verts, ragged_opt_batch
+        if kind == "deep":
+            _, batch = oracle_two_hand_verts(mano_arrays, B, DEEP_SEED, overlap="deep")
+        elif B == 3:
+            _, batch = oracle_two_hand_verts(mano_arrays, 8, 2608)
+            batch = {k: v[:B].clone() for k, v in ragged_opt_batch(batch).items()}
+            assert (batch["hand_type_array"] == torch.tensor([1.0, 0.0])).all(dim=1).any()
+        else:
+            _, batch = oracle_two_hand_verts(mano_arrays, B, 2604 if B == 1 else 1700 + B)
+        if kind == "far":
+            batch = {k: v.clone() for k, v in batch.items()}
+            batch["init_hand_trans"].reshape(B, -1)[:, 0] += 1.0
+        _BATCHES[key] = batch
+    return _BATCHES[key]
+
+
+def _stages(epoch, which):
+    from ihmr_amd.strategies import make_opt_strategy
+    trans, orient, pose, shape = make_opt_strategy(epoch)
+    if which == "trans":
+        return [trans]
+    if which == "trans-cam":
+        return [dict(trans, update_params=["pred_hand_trans", "pred_cam_params"])]
+    if which == "shape":
+        return [shape]
+    if which == "left-shape":
+        return [dict(shape, update_params=["pred_left_shape_params"])]
+    assert which == "all"
+    return [trans, orient, pose, shape]
+
+
+def _run(batch, B, epoch, freq, which, generic=False, full=True, **extra):
+    """One fresh instance (its stage graphs are captured under the switch), two passes (capture, replay).  full: optimize() as the
+    driver runs it (the closing forward included); otherwise the stages alone."""
+    from ihmr_amd import hip
+    from ihmr_amd.optimize_model import OptimizeModel
+    prev = hip.lib().ihmr_debug_force_generic_tail(1 if generic else 0)
+    try:
+        m = OptimizeModel(_make_opt(B, epoch, freq, **extra))
+        m.strategy = _stages(epoch, which)
+        for rep in range(2):
+            m.set_input(batch); m.init_optimize(); m.optimize()
+            torch.cuda.synchronize()
+    finally:
+        hip.lib().ihmr_debug_force_generic_tail(prev)
+    out = {f"export/{k}": np.ascontiguousarray(v) for k, v in m.get_pred_result().items() if isinstance(v, np.ndarray)}
+    out.update({f"state/{k}": m.buf[k].cpu().numpy() for k in STATE_KEYS})
+    out["selected_history"] = torch.stack(m.selected_history).cpu().numpy()
+    return out
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32) if a.dtype.itemsize == 4 else a.view(np.uint8)
+
+
+def _assert_same(a, b, what):
+    assert a.keys() == b.keys()
+    for k in a:
+        assert a[k].shape == b[k].shape and np.array_equal(_bits(a[k]), _bits(b[k])), f"{what}: {k} differs"
+
+
+def _check(batch, B, epoch, freq, which, translated_pair=False, **extra):
+    new = _run(batch, B, epoch, freq, which, **extra)
+    _assert_same(new, _run(batch, B, epoch, freq, which, generic=True, **extra), "stage tails vs generic tail forms")
+    _assert_same(new, _run(batch, B, epoch, freq, which, no_fused_tail=True, **extra), "stage tails vs separate launches")
+    if translated_pair:
+        a = _run(batch, B, epoch, freq, which, sdf_no_translated_reuse=True, **extra)
+        b = _run(batch, B, epoch, freq, which, sdf_no_translated_reuse=True, no_fused_tail=True, **extra)
+        _assert_same(a, b, "stage tails vs separate launches, left hand's grid rebuilt")
+    return new
+
+
+@pytest.mark.parametrize("kind", ["default", "deep"])
+@pytest.mark.parametrize("freq", [1, 2])
+@pytest.mark.parametrize("n_iters", [1, 2, 5])
+@pytest.mark.parametrize("B", [1, 3])
+def test_translation_stage_alone(mano_arrays, B, n_iters, freq, kind):
+    """n_iters = 1 launches no STEP tail, n_iters = 2 makes the filling launch and the stage's last launch neighbours, n_iters = 5 runs
+    three launches on the kept vertices; B = 1: workgroup 0 also zeroes the collision counters."""
+    batch = _batch(mano_arrays, kind, B)
+    out = _check(batch, B, n_iters - 1, freq, "trans", translated_pair=True)
+    if n_iters > 1:
+        assert np.abs(out["state/adam_m"][:, 3:6]).max() > 0, "the stage computed no translation gradient"
+        assert np.abs(out["state/adam_m"][:, 6:]).max() == 0
+
+
+def test_translation_and_camera_in_one_stage(mano_arrays):
+    batch = _batch(mano_arrays, "default", 3)
+    out = _check(batch, 3, 2, 1, "trans-cam", translated_pair=True)
+    assert np.abs(out["state/adam_m"][:, 0:3]).max() > 0 and np.abs(out["state/adam_m"][:, 3:6]).max() > 0
+
+
+@pytest.mark.parametrize("B,fuse", [(3, 1), (64, 1), (3, 2)])
+def test_opt_default_epoch_2(mano_arrays, B, fuse):
+    """4 x 3 iterations through optimize(): the hand-over from the translation stage (right-hand vertices never rewritten, the
+    candidate lists kept) to the orientation stage, and the shape stage behind the finger-pose stage; once with two fused batches."""
+    batch = _batch(mano_arrays, "default", B)
+    if fuse > 1:
+        batch = {k: torch.cat([v] * fuse, dim=0) for k, v in batch.items()}
+    out = _check(batch, B, 2, 1, "all", fuse_batches=fuse)
+    assert np.abs(out["state/adam_m"][:, 102:]).max() > 0
+
+
+@pytest.mark.parametrize("kind", ["far", "default", "deep"])
+def test_shape_stage_alone(mano_arrays, kind):
+    """far: only the fingertip vertices carry a gradient; deep: most vertices do.  The optimizer state after ONE iteration is
+    (1 - beta1) x the shape gradient (+ the regulariser, computed the same way in every run): g_shape of the first iteration
+    compared on its own."""
+    batch = _batch(mano_arrays, kind, 3)
+    first = _check(batch, 3, 0, 1, "shape")
+    assert np.abs(first["state/adam_m"][:, 102:]).max() > 0, "no shape gradient"
+    out = _check(batch, 3, 2, 1, "shape")
+    if kind == "far":
+        assert np.abs(out["state/loss_batch"][2]).max() == 0, "the far batch collides"
+    else:
+        assert np.abs(out["state/loss_batch"][2]).max() > 0, "no collision on this batch"
+
+
+def test_left_shape_only_stage(mano_arrays):
+    """Only `pred_left_shape_params` is refined: the right hand keeps its rotations AND its shape, the left hand's wrist and with it
+    its shift move."""
+    batch = _batch(mano_arrays, "default", 3)
+    out = _check(batch, 3, 2, 1, "left-shape")
+    assert np.abs(out["state/adam_m"][:, 112:]).max() > 0 and np.abs(out["state/adam_m"][:, 102:112]).max() == 0
