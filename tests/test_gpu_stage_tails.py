@@ -32,29 +32,10 @@ def _make_opt(B, epoch, freq, **extra):
                                  optimizer="adam", opt_epoch=epoch, **extra)
 
 
-_BATCHES = {}
-
-
 def _batch(mano_arrays, kind, B):
-    """default: the synthetic batch (B = 3: control / right hand only / left hand only -- a (1, 0) sample, collision gradient scale 0);
-    deep: the deep-overlap hands of the deep-interpenetration tests; far: the default batch with the left hands moved a metre away
-    (no collision: only the fingertip gradients are non-zero).  Built once, handed out unchanged."""
-    key = (kind, B)
-    if key not in _BATCHES:
-        from helpers import DEEP_SEED, oracle_two_hand_verts, ragged_opt_batch
-        if kind == "deep":
-            _, batch = oracle_two_hand_verts(mano_arrays, B, DEEP_SEED, overlap="deep")
-        elif B == 3:
-            _, batch = oracle_two_hand_verts(mano_arrays, 8, 2608)
-            batch = {k: v[:B].clone() for k, v in ragged_opt_batch(batch).items()}
-            assert (batch["hand_type_array"] == torch.tensor([1.0, 0.0])).all(dim=1).any()
-        else:
-            _, batch = oracle_two_hand_verts(mano_arrays, B, 2604 if B == 1 else 1700 + B)
-        if kind == "far":
-            batch = {k: v.clone() for k, v in batch.items()}
-            batch["init_hand_trans"].reshape(B, -1)[:, 0] += 1.0
-        _BATCHES[key] = batch
-    return _BATCHES[key]
+    """The batches of tests/stage_cases.py (default / deep / far), built once, handed out unchanged."""
+    from stage_cases import batch
+    return batch(mano_arrays, kind, B)
 
 
 def _stages(epoch, which):
