@@ -25,6 +25,7 @@
 #include "train_conv.h"
 #include "copy_pack.h"
 #include "launch_plan.h"
+#include "stage_plan.h"
 
 // bench.py's per-kernel timer -- the library's ONE piece of process-global state (include/ihmr_hip.h says so): the pointer and the
 // list of pending event pairs are shared by every stream and thread of the process, guarded by g_timer_mutex; while no timer is set
@@ -230,10 +231,11 @@ extern "C" int ihmr_mano_update_shapedirs(ihmr_mano* m, const float* shapedirs_h
 extern "C" size_t ihmr_mano_workspace_bytes(int N) { return lbs_ws_bytes(N); }
 
 // the skinning launch (REUSE: the workspace holds v_posed of the current pose and shape parameters, see lbs_skin_kernel)
-// small launches: four instead of eight hands per skin workgroup (half the chain per thread)
+static_assert(plan::SKIN_SMALL_MAX_HANDS == LBS_SMALL_MAX_HANDS && plan::BWD2_LDS_MIN_HANDS == LBS_B2_MIN_HANDS &&
+              plan::PREP_SMALL_MAX_HANDS == SDF_PREP_SMALL_MAX_HANDS, "stage_plan.h restates the launch-form thresholds of the kernel headers");
 template <bool TWO_HAND, int MODE>
 static void lbs_skin_launch_mode(const ihmr_mano* m, int N, int B, float* verts, float* joints, const LbsWork& wk, float* pose_off, hipStream_t st) {
-    const bool small = N <= LBS_SMALL_MAX_HANDS;
+    const bool small = plan::skin_small(N);
     const int hg8 = 8 * (small ? LBS_HG_SMALL : LBS_HG);
     const dim3 skin_grid(8, 4 * ((N + hg8 - 1) / hg8));
     if (small) hipLaunchKernelGGL((lbs_skin_kernel<TWO_HAND, MODE, LBS_HG_SMALL>), skin_grid, dim3(LBS_THREADS), 0, st, *m, (const float*)wk.skel, N, B,
@@ -241,12 +243,13 @@ static void lbs_skin_launch_mode(const ihmr_mano* m, int N, int B, float* verts,
     else hipLaunchKernelGGL((lbs_skin_kernel<TWO_HAND, MODE, LBS_HG>), skin_grid, dim3(LBS_THREADS), 0, st, *m, (const float*)wk.skel, N, B, verts,
                             joints, wk.v_posed, pose_off);
 }
-// skin modes of the callers: FULL (both blends), REUSE (v_posed kept: lbs_skin_kernel), FULL_STORE_P (both blends + the pose offsets P stored:
-// the first iteration of a stage that moves the shape but not the finger pose), KEEP_P (the later iterations of such a stage: no pose rows read)
+// skin modes of the callers: plan::Skin (stage_plan.h)
 #define LBS_SKIN_FULL 0
 #define LBS_SKIN_REUSE 1
 #define LBS_SKIN_KEEP_P 2
 #define LBS_SKIN_FULL_STORE_P 3
+static_assert(plan::SKIN_FULL == LBS_SKIN_FULL && plan::SKIN_REUSE == LBS_SKIN_REUSE && plan::SKIN_KEEP_P == LBS_SKIN_KEEP_P &&
+              plan::SKIN_FULL_STORE_P == LBS_SKIN_FULL_STORE_P, "stage_plan.h restates the skin modes");
 static int g_force_full_skin = 0;    // checker switch: ihmr_debug_force_full_skin
 template <bool TWO_HAND>
 static void lbs_skin_launch(const ihmr_mano* m, int mode, int N, int B, float* verts, float* joints, const LbsWork& wk, hipStream_t st) {
@@ -298,9 +301,7 @@ static void lbs_backward_launch(const ihmr_mano* m, bool two_hand, int N, int B,
         hipLaunchKernelGGL(lbs_bwd1_kernel<false>, dim3(N), dim3(LBS_THREADS), part_lds, st, *m, wk, B, d_verts, d_joints, d_orient,
                            d_betas, d_trans, need_mask);
     if (need_mask & 2) {
-        // LDS-tiled form from LBS_B2_MIN_HANDS = 256 hands on (one batch of 64 samples = 128 hands: 2 x 25 workgroups are too few; the
-        // streaming form stays there); the same bits either way
-        if (N >= LBS_B2_MIN_HANDS && !g_bwd2_streaming) hipLaunchKernelGGL(lbs_bwd2_lds_kernel, dim3((N + 63) / 64, LBS_KG), dim3(320), 0, st, *m, wk, N);
+        if (plan::bwd2_lds(N, g_bwd2_streaming)) hipLaunchKernelGGL(lbs_bwd2_lds_kernel, dim3((N + 63) / 64, LBS_KG), dim3(320), 0, st, *m, wk, N);
         else hipLaunchKernelGGL(lbs_bwd2_kernel, dim3(5, (N + 31) / 32, LBS_KG), dim3(64), 0, st, *m, wk, N);
         if (two_hand) hipLaunchKernelGGL(lbs_bwd3_kernel<true>, dim3(N), dim3(64), 0, st, wk, N, B, d_pose);
         else hipLaunchKernelGGL(lbs_bwd3_kernel<false>, dim3(N), dim3(64), 0, st, wk, N, B, d_pose);
@@ -351,16 +352,15 @@ static int sdf_launch(const VertLayout& vl, const int32_t* faces_r_soa, const in
     // on seam C); the prep kernel appends to it
     // an inside-list entry is (hand << 16) | voxel with bit 31 reserved (SDF_ENT_REFUSED): hand ids stay below 32768
     if (B <= 0 || 2 * B > SDF_MAX_HANDS) return -1;
-    // small launches: the 1024-thread form (half the chain per thread), see sdf_collision.h
-    const bool small = 2 * B <= SDF_PREP_SMALL_MAX_HANDS;
+    const int prep = plan::prep_form(2 * B, dense);      // (see sdf_collision.h)
     ws.fpk[0] = fpk_r; ws.fpk[1] = fpk_l; ws.B = B;
     const bool timed = g_timer != nullptr;
     hipEvent_t tcur;
     if (timed) { if (int rc = timed_begin(&tcur, st)) return rc; }
-    if (dense)
+    if (prep == plan::PREP_DENSE)
         hipLaunchKernelGGL((sdf_prep_kernel<true, SDF_PREP_THREADS_LARGE>), dim3(2 * B), dim3(SDF_PREP_THREADS_LARGE), 0, st, vl, B, faces_r_soa,
                            faces_l_soa, ws, g_collect_stats);
-    else if (small)
+    else if (prep == plan::PREP_SMALL)
         hipLaunchKernelGGL((sdf_prep_kernel<false, SDF_PREP_THREADS_SMALL>), dim3(2 * B), dim3(SDF_PREP_THREADS_SMALL), 0, st, vl, B, faces_r_soa,
                            faces_l_soa, ws, g_collect_stats);
     else
@@ -399,6 +399,15 @@ __global__ void faces_to_soa_kernel(const int32_t* __restrict__ aos, int32_t* __
     }
     packed[f] = pk;
 }
+// both hands' SoA and packed copies, carved from the tail of the caller's workspace (the first launch also zeroes the counters of `ws`)
+struct FaceCopies { const int32_t *soa_r, *soa_l; const uint32_t *pk_r, *pk_l; };
+static FaceCopies faces_to_workspace(const int32_t* faces_right, const int32_t* faces_left, void* workspace, int B, const SdfWorkspace& ws, hipStream_t st) {
+    int32_t* soa = (int32_t*)((char*)workspace + sdf_ws_bytes(2 * B));
+    uint32_t* pk = (uint32_t*)(soa + 6 * NFP);
+    hipLaunchKernelGGL(faces_to_soa_kernel, dim3((NFP + 255) / 256), dim3(256), 0, st, faces_right, soa, pk, ws.inside_count);
+    hipLaunchKernelGGL(faces_to_soa_kernel, dim3((NFP + 255) / 256), dim3(256), 0, st, faces_left, soa + 3 * NFP, pk + NFP, (int*)nullptr);
+    return FaceCopies{soa, soa + 3 * NFP, pk, pk + NFP};
+}
 
 extern "C" int ihmr_sdf_collision_ex(const int32_t* faces_right, const int32_t* faces_left, const float* hand_verts, int B,
                                      float robustifier, const ihmr_sdf_options* options, float* loss, float* per_vert,
@@ -411,12 +420,9 @@ extern "C" int ihmr_sdf_collision_ex(const int32_t* faces_right, const int32_t* 
         if (options->loss_divisor > 0.f) ws.loss_div = options->loss_divisor;
         ws.swap_xz = options->swap_xz ? 1 : 0;
     }
-    int32_t* soa = (int32_t*)((char*)workspace + sdf_ws_bytes(2 * B));
-    uint32_t* pk = (uint32_t*)(soa + 6 * NFP);
-    hipLaunchKernelGGL(faces_to_soa_kernel, dim3((NFP + 255) / 256), dim3(256), 0, st, faces_right, soa, pk, ws.inside_count);
-    hipLaunchKernelGGL(faces_to_soa_kernel, dim3((NFP + 255) / 256), dim3(256), 0, st, faces_left, soa + 3 * NFP, pk + NFP, (int*)nullptr);
+    const FaceCopies f = faces_to_workspace(faces_right, faces_left, workspace, B, ws, st);
     VertLayout vl{hand_verts, (long)2 * NV3, (long)NV3};
-    return sdf_launch(vl, soa, soa + 3 * NFP, pk, pk + NFP, B, ws, robustifier, loss, per_vert, origin_scale, dval, false, st);
+    return sdf_launch(vl, f.soa_r, f.soa_l, f.pk_r, f.pk_l, B, ws, robustifier, loss, per_vert, origin_scale, dval, false, st);
 }
 
 extern "C" int ihmr_sdf_collision(const int32_t* faces_right, const int32_t* faces_left, const float* hand_verts, int B,
@@ -431,12 +437,9 @@ extern "C" int ihmr_sdf_dense_grid(const int32_t* faces_right, const int32_t* fa
     if (!workspace || B <= 0 || 2 * B > SDF_MAX_HANDS) return -1;
     hipStream_t st = (hipStream_t)stream;
     SdfWorkspace ws = sdf_carve(workspace, 2 * B);
-    int32_t* soa = (int32_t*)((char*)workspace + sdf_ws_bytes(2 * B));
-    uint32_t* pk = (uint32_t*)(soa + 6 * NFP);
-    hipLaunchKernelGGL(faces_to_soa_kernel, dim3((NFP + 255) / 256), dim3(256), 0, st, faces_right, soa, pk, ws.inside_count);
-    hipLaunchKernelGGL(faces_to_soa_kernel, dim3((NFP + 255) / 256), dim3(256), 0, st, faces_left, soa + 3 * NFP, pk + NFP, (int*)nullptr);
+    const FaceCopies f = faces_to_workspace(faces_right, faces_left, workspace, B, ws, st);
     VertLayout vl{hand_verts, (long)2 * NV3, (long)NV3};
-    int rc = sdf_launch(vl, soa, soa + 3 * NFP, pk, pk + NFP, B, ws, 0.f, nullptr, nullptr, nullptr, nullptr, true, st);
+    int rc = sdf_launch(vl, f.soa_r, f.soa_l, f.pk_r, f.pk_l, B, ws, 0.f, nullptr, nullptr, nullptr, nullptr, true, st);
     if (rc) return rc;
     // workspace order is hand = hnd*B + b; the caller's grid is (B,2,...)
     for (int b = 0; b < B; ++b)
@@ -451,148 +454,102 @@ extern "C" size_t ihmr_opt_workspace_bytes(int B) { return opt_ws_bytes(B); }
 
 // `prev` = the Adam step of the previous iteration (group < 0: none), applied at the head of the skeleton kernel
 static const ParamStep kNoStep{0, 0.f, 0.f, 1.f, -1, 0, 0};
-// skin_mode: LBS_SKIN_REUSE = the workspace holds v_posed of the current pose and shape parameters (see lbs_skin_kernel); < 0: no skin launch
-// lists: temporal candidate lists of the collision kernels -- 0 off (single-shot callers), 1 reuse while valid, 2 rebuild now, 3 = the first
-// iteration of a stage whose caller vouches for the lists of the previous stage (ihmr_opt_stage::keep_lists): the static-hand bookkeeping
-// starts over, a hand's lists stay while its own displacement test passes
-// the collision workspace of the fused loop with the switches of this call
-// static_mask: bit 0 / 1 = the right / left hands have had bit-identical vertices since the stage's first iteration (SdfWorkspace::static_mask)
-static SdfWorkspace opt_sdf_ws(const ihmr_opt_io* io, const OptWork& wk, int B, int lists, int static_mask = 0) {
+// the collision workspace of one iteration with the switches of this call (plan::plan_sdf_flags)
+static SdfWorkspace opt_sdf_ws(const ihmr_opt_io* io, const OptWork& wk, int B, int lists, int static_mask) {
     SdfWorkspace ws = sdf_carve(wk.sdf_ws, 2 * B, true);
-    ws.list_mode = (lists != 0 && !io->sdf_no_candidate_lists) ? 1 : 0;
-    ws.force_rebuild = lists == 2 ? 1 : 0;
-    ws.static_stage = (ws.list_mode && io->sdf_no_static_reuse != 1) ? (static_mask & 3) : 0;
-    ws.static_mask = lists >= 2 ? 0 : ws.static_stage;
-    ws.moving_box = (static_mask >> 2) & ws.static_stage;      // (bits 2-3 of the caller's mask: sides that only translate)
+    const plan::SdfFlags f = plan::plan_sdf_flags(lists, static_mask, io->sdf_no_candidate_lists, io->sdf_no_static_reuse);
+    ws.list_mode = f.list_mode;
+    ws.force_rebuild = f.force_rebuild;
+    ws.static_stage = f.static_stage;
+    ws.static_mask = f.static_mask;
+    ws.moving_box = f.moving_box;
     ws.align_corners = io->sdf_align_corners ? 1 : 0;
     if (io->sdf_loss_divisor > 0.f) ws.loss_div = io->sdf_loss_divisor;
     ws.swap_xz = io->sdf_swap_xz ? 1 : 0;
     return ws;
 }
 
-// head = the Adam + skeleton launch, skin = the skinning launch, tail = the sampling + loss launch (a caller that fuses them into other launches skips them)
-static int opt_forward(const ihmr_mano* m, const ihmr_mano* m_left, const ihmr_opt_io* io, const OptWork& wk, int B,
-                       const ihmr_opt_weights& w, const ParamStep& prev, hipStream_t st, int need_cam = 0, int skin_mode = LBS_SKIN_FULL,
-                       int lists = 0, bool head = true, bool tail = true, int static_mask = 0, const MlpSelect* sel = nullptr) {
-    if (head)
-        hipLaunchKernelGGL(opt_adam_skel_kernel, dim3(B), dim3(384), 0, st, *m, *io, wk, B, prev, sdf_carve(wk.sdf_ws, 2 * B, true).inside_count);
-    // (skin_mode < 0: the tail launch of the previous iteration has skinned the stored v_posed with the new skeletons, opt_tail_kernel<true, true>)
-    if (skin_mode >= 0) lbs_skin_launch<true>(m, skin_mode, 2 * B, B, io->verts, wk.joints_raw, wk.lbs, st);
-    SdfWorkspace ws = opt_sdf_ws(io, wk, B, lists, static_mask);
+// what every launch of the refinement loop is handed; sel: the accept / reject step of an IHMR-MLP evaluation, or none
+struct OptCtx {
+    const ihmr_mano *m, *m_left;
+    const ihmr_opt_io* io;
+    OptWork wk;
+    int B;
+    const ihmr_opt_weights* w;
+    hipStream_t st;
+    const MlpSelect* sel;
+};
+
+// The launches of one iteration, exactly as `q` lists them (plan::IterPlan): head = the Adam + skeleton launch applying `prev`, skin = the
+// skinning launch, the collision prep + distance launches, the tail -- which in its stepping forms applies `next` -- and the LBS backward
+static int run_iteration(const OptCtx& c, const plan::IterPlan& q, const ParamStep& prev, const ParamStep& next) {
+    const ihmr_mano* m = c.m;
+    const ihmr_opt_io* io = c.io;
+    const OptWork& wk = c.wk;
+    const int B = c.B;
+    hipStream_t st = c.st;
+    const SdfWorkspace ws = opt_sdf_ws(io, wk, B, q.lists, q.static_mask);
+    if (q.head) hipLaunchKernelGGL(opt_adam_skel_kernel, dim3(B), dim3(384), 0, st, *m, *io, wk, B, prev, ws.inside_count);
+    if (q.skin != plan::SKIN_NONE) lbs_skin_launch<true>(m, q.skin, 2 * B, B, io->verts, wk.joints_raw, wk.lbs, st);
+    if (q.tail == plan::TAIL_NONE) return (int)hipGetLastError();
     VertLayout vl{io->verts, (long)NV3, (long)B * NV3};
-    int rc = sdf_launch(vl, m->faces, m_left ? m_left->faces : m->faces, m->faces_pk, m_left ? m_left->faces_pk : m->faces_pk, B, ws, 0.f,
+    int rc = sdf_launch(vl, m->faces, c.m_left ? c.m_left->faces : m->faces, m->faces_pk, c.m_left ? c.m_left->faces_pk : m->faces_pk, B, ws, 0.f,
                         nullptr, nullptr, nullptr, nullptr, false, st);
     if (rc) return rc;
-    // collision sampling (loss_batch[2], masked by hand type; gradient -> g_verts) and the joint losses in one launch
-    MlpSelect no_sel;
-    memset(&no_sel, 0, sizeof(no_sel));
-    if (tail) hipLaunchKernelGGL(opt_sample_loss_kernel, dim3(B), dim3(SDF_SAMPLE_THREADS), 0, st, *io, wk, B, w, vl, ws, need_cam, sel ? *sel : no_sel);
+    if (q.tail == plan::TAIL_SEPARATE) {
+        // collision sampling (loss_batch[2], masked by hand type; gradient -> g_verts) and the joint losses in one launch
+        MlpSelect no_sel;
+        memset(&no_sel, 0, sizeof(no_sel));
+        hipLaunchKernelGGL(opt_sample_loss_kernel, dim3(B), dim3(SDF_SAMPLE_THREADS), 0, st, *io, wk, B, *c.w, vl, ws, q.need_cam, c.sel ? *c.sel : no_sel);
+    } else {
+        const size_t tail_lds = (size_t)opt_tail_dynamic_lds(m->nseg);
+        hipEvent_t tcur;
+        const bool timed = g_timer != nullptr;
+        if (timed) { if (int rc2 = timed_begin(&tcur, st)) return rc2; }
+        const TailArgs ta{*m, *io, wk, B, *c.w, vl, ws, q.need_cam, q.need_mask, next, ws.inside_count, q.keep_rot, q.first};
+        if (q.tail == plan::TAIL_TRANS)
+            hipLaunchKernelGGL(opt_tail_kernel_trans, dim3(B), dim3(SDF_SAMPLE_THREADS), 0, st, ta);
+        else if (q.tail == plan::TAIL_STEP_SKIN)
+            hipLaunchKernelGGL((opt_tail_kernel<true, true>), dim3(B), dim3(SDF_SAMPLE_THREADS), tail_lds, st, ta);
+        else if (q.tail == plan::TAIL_STEP)
+            hipLaunchKernelGGL(opt_tail_kernel<true>, dim3(B), dim3(SDF_SAMPLE_THREADS), tail_lds, st, ta);
+        else
+            hipLaunchKernelGGL(opt_tail_kernel<false>, dim3(B), dim3(SDF_SAMPLE_THREADS), tail_lds, st, ta);
+        if (timed) { if (int rc2 = timed_next(&tcur, IHMR_TIMED_OPT_TAIL, st)) return rc2; (void)hipEventDestroy(tcur); }
+    }
+    if (q.after != plan::AFTER_NONE)
+        lbs_backward_launch(m, true, 2 * B, B, wk.g_verts, wk.g_joints, wk.g_orient, wk.g_pose, wk.g_shape, wk.g_trans, q.need_mask, wk.lbs, st,
+                            /*bwd1_done=*/q.after == plan::AFTER_BWD23);
     return (int)hipGetLastError();
 }
 
 extern "C" int ihmr_opt_forward_losses(const ihmr_mano* m, const ihmr_mano* m_left, const ihmr_opt_io* io, int B,
                                        const ihmr_opt_weights* w, void* stream) {
     if (!m || !io || !w || B <= 0 || 2 * B > SDF_MAX_HANDS) return -1;
-    hipStream_t st = (hipStream_t)stream;
-    OptWork wk = opt_carve(io->workspace, B);
-    int rc = opt_forward(m, m_left, io, wk, B, *w, kNoStep, st);
-    if (rc) return rc;
-    return (int)hipGetLastError();
+    return run_iteration(OptCtx{m, m_left, io, opt_carve(io->workspace, B), B, w, (hipStream_t)stream, nullptr}, plan::kForwardLosses, kNoStep, kNoStep);
 }
+
+static_assert(plan::PB_CAM == IHMR_PB_CAM && plan::PB_TRANS == IHMR_PB_TRANS && plan::PB_ORIENT_R == IHMR_PB_ORIENT_R &&
+              plan::PB_ORIENT_L == IHMR_PB_ORIENT_L && plan::PB_POSE_R == IHMR_PB_POSE_R && plan::PB_POSE_L == IHMR_PB_POSE_L &&
+              plan::PB_SHAPE_R == IHMR_PB_SHAPE_R && plan::PB_SHAPE_L == IHMR_PB_SHAPE_L, "stage_plan.h restates the parameter-block bits");
+static_assert(plan::OPTIM_ADAM == IHMR_OPTIM_ADAM && plan::OPTIM_SGD == IHMR_OPTIM_SGD, "stage_plan.h restates the optimizers");
 
 extern "C" int ihmr_opt_run_stage(const ihmr_mano* m, const ihmr_mano* m_left, const ihmr_opt_io* io, int B,
                                   const ihmr_opt_weights* w, const ihmr_opt_stage* sg, void* stream) {
-    if (!m || !io || !w || !sg || B <= 0 || 2 * B > SDF_MAX_HANDS || sg->n_iters <= 0 || sg->save_freq <= 0) return -1;
-    if (sg->param_mask <= 0 || sg->param_mask > 255 || sg->select_loss < 0 || sg->select_loss > 2) return -1;
-    if (sg->optimizer != IHMR_OPTIM_ADAM && sg->optimizer != IHMR_OPTIM_SGD) return -1;
-    hipStream_t st = (hipStream_t)stream;
-    OptWork wk = opt_carve(io->workspace, B);
-    const int pm = sg->param_mask;
-    // what the LBS backward has to deliver (bit0 orient, bit1 pose, bit2 betas, bit3 trans)
-    const int need_mask = ((pm & (IHMR_PB_ORIENT_R | IHMR_PB_ORIENT_L)) ? 1 : 0) | ((pm & (IHMR_PB_POSE_R | IHMR_PB_POSE_L)) ? 2 : 0) |
-                          ((pm & (IHMR_PB_SHAPE_R | IHMR_PB_SHAPE_L)) ? 4 : 0) | ((pm & IHMR_PB_TRANS) ? 8 : 0);
-    const int need_cam = (pm & IHMR_PB_CAM) ? 1 : 0, sgd = sg->optimizer == IHMR_OPTIM_SGD;
-    int S = 0;
+    if (!m || !io || !w || !sg || B <= 0 || 2 * B > SDF_MAX_HANDS) return -1;
+    if (!plan::stage_ok(sg->param_mask, sg->optimizer, sg->n_iters, sg->save_freq, sg->select_loss)) return -1;
+    const OptCtx c{m, m_left, io, opt_carve(io->workspace, B), B, w, (hipStream_t)stream, nullptr};
+    const plan::StagePlan p = plan::plan_stage(sg->param_mask, io->no_fused_tail, m->tail_fits, io->sdf_no_static_reuse, g_force_generic_tail, sg->keep_lists);
+    const int sgd = sg->optimizer == IHMR_OPTIM_SGD;
     ParamStep step{0, 0.f, 0.f, 1.f, -1, 1, 0};   // iteration 0: no step yet, zero the optimizer state
-    // a stage that moves neither the finger pose nor the shape keeps v_posed: computed in its first iteration, reused after
-    const bool vposed_fixed = (pm & (IHMR_PB_POSE_R | IHMR_PB_POSE_L | IHMR_PB_SHAPE_R | IHMR_PB_SHAPE_L)) == 0;
-    // ... and a stage that moves the shape but not the finger pose keeps the pose offsets P: stored by its first iteration's skinning, reused
-    // after (lbs_skin_kernel MODE KEEP_P: the 1.8 MB pose basis is not read again; the same bits, test_skin_keeps_pose_offsets_bit_identically)
-    const bool pose_fixed = (pm & (IHMR_PB_POSE_R | IHMR_PB_POSE_L)) == 0;
-    const int keep_mode = vposed_fixed ? LBS_SKIN_REUSE : (pose_fixed ? LBS_SKIN_KEEP_P : LBS_SKIN_FULL);
-    const int first_mode = (!vposed_fixed && pose_fixed) ? LBS_SKIN_FULL_STORE_P : LBS_SKIN_FULL;
-    // The tail of an iteration -- sampling + losses, LBS backward of both hands, and in the stages that do not move the finger pose also the
-    // optimizer step + next skeletons -- is ONE launch per sample (opt_tail_kernel): 4 launches per iteration instead of 6 (finger-pose
-    // stage, whose backward continues with a batch-wide GEMM: 7 instead of 8); in a stage that keeps v_posed the same launch also skins
-    // the next iteration's vertices: 3 launches (skin_mode < 0 below)
-    const bool fused_tail = need_mask != 0 && !io->no_fused_tail && m->tail_fits;
-    // Hands whose vertices cannot change during this stage (SdfWorkspace::static_mask): the right hand when none of its own blocks is
-    // refined; the left hand when neither its own blocks, nor the translation, nor the right hand's shape (the left hand is shifted by
-    // trans + J_r[0] - J_l[0], optimize_model.py:217-224) is.  opt_default's translation stage: the right hands.
-    int static_mask = ((pm & (IHMR_PB_ORIENT_R | IHMR_PB_POSE_R | IHMR_PB_SHAPE_R)) ? 0 : 1) |
-                      ((pm & (IHMR_PB_ORIENT_L | IHMR_PB_POSE_L | IHMR_PB_SHAPE_L | IHMR_PB_TRANS | IHMR_PB_SHAPE_R)) ? 0 : 2);
-    // Round 5: a left hand that the stage only TRANSLATES (the translation stage of opt_default: trans alone moves) is static in its own
-    // normalised frame -- its box follows it, everything inside the box stays: treated as static with a moving box (SdfWorkspace::moving_box;
-    // bits 2-3 of the mask).  The kept grid is the first iteration's; a recomputation would differ by the rounding of the translated
-    // vertices, so unlike the static reuse this is not bit-identical to the from-scratch path (sdf_no_static_reuse = 2 switches it off).
-    if ((pm & IHMR_PB_TRANS) && !(pm & (IHMR_PB_ORIENT_L | IHMR_PB_POSE_L | IHMR_PB_SHAPE_L | IHMR_PB_SHAPE_R)) && io->sdf_no_static_reuse == 0)
-        static_mask |= 2 | (2 << 2);
-    const bool pose_stage = (need_mask & 2) != 0;
-    // Each stage's tail does only what that stage can move (ihmr_debug_force_generic_tail switches both off):
-    //   * only the translation (and the camera) moves: opt_tail_kernel_trans -- the right hand is left alone, the left hand's vertices are
-    //     the kept pre-shift values plus the new shift;
-    //   * a hand none of whose axis-angles is refined keeps the rotations and the pose feature of its skeleton record in the STEP tails
-    //     (lbs_skel_hand: keep_rot; the record is in LDS whenever the LBS backward runs, need_mask & 7).  opt_default: the shape stage
-    const bool trans_tail = vposed_fixed && need_mask == 8 && !g_force_generic_tail;
-    const int keep_rot = ((need_mask & 7) == 0 || g_force_generic_tail) ? 0
-                         : (((pm & (IHMR_PB_ORIENT_R | IHMR_PB_POSE_R)) ? 0 : 1) | ((pm & (IHMR_PB_ORIENT_L | IHMR_PB_POSE_L)) ? 0 : 2));
-    const size_t tail_lds = (size_t)opt_tail_dynamic_lds(m->nseg);
-    const int lists_first = sg->keep_lists ? 3 : 2;
     for (int it = 0; it < sg->n_iters; ++it) {
-        // the first iteration of a stage starts the candidate lists over (the workspace is the caller's memory: whatever it holds, a stage
-        // is self-contained) -- unless the caller vouches for them (keep_lists): then a hand keeps its lists while the prep kernel's
-        // displacement test against the reference pose they were built at passes, whether an optimizer step or the previous stage's
-        // select step moved the hand
-        const double t = (double)(it + 1);
-        const double bc1 = 1.0 - pow(0.9, t), bc2 = 1.0 - pow(0.999, t);
-        const ParamStep next{pm, w->shape_reg, sgd ? sg->lr : (float)((double)sg->lr / bc1), (float)sqrt(bc2),
-                             (it % sg->save_freq == 0) ? S++ : -1, 0, sgd};
-        if (fused_tail) {
-            // head (optimizer step of the previous iteration + skeletons): stand-alone in the first iteration (zero the optimizer state,
-            // first skeletons) and in the finger-pose stage; otherwise the tail of iteration it - 1 has done it
-            // ... and in a stage that keeps v_posed (translation, orientation) the tail has skinned the next vertices as well: 3 launches
-            int rc = opt_forward(m, m_left, io, wk, B, *w, step, st, need_cam, it == 0 ? first_mode : (vposed_fixed ? -1 : keep_mode), it == 0 ? lists_first : 1,
-                                 /*head=*/it == 0 || pose_stage, /*tail=*/false, static_mask);
-            if (rc) return rc;
-            SdfWorkspace ws = opt_sdf_ws(io, wk, B, it == 0 ? lists_first : 1, static_mask);
-            VertLayout vl{io->verts, (long)NV3, (long)B * NV3};
-            hipEvent_t tcur;
-            const bool timed = g_timer != nullptr;
-            if (timed) { if (int rc2 = timed_begin(&tcur, st)) return rc2; }
-            const TailArgs ta{*m, *io, wk, B, *w, vl, ws, need_cam, need_mask, next, ws.inside_count, keep_rot, it == 0 ? 1 : 0};
-            if (trans_tail && it + 1 < sg->n_iters)
-                hipLaunchKernelGGL(opt_tail_kernel_trans, dim3(B), dim3(SDF_SAMPLE_THREADS), 0, st, ta);
-            else if (vposed_fixed && it + 1 < sg->n_iters)
-                hipLaunchKernelGGL((opt_tail_kernel<true, true>), dim3(B), dim3(SDF_SAMPLE_THREADS), tail_lds, st, ta);
-            else if (!pose_stage && it + 1 < sg->n_iters)
-                hipLaunchKernelGGL(opt_tail_kernel<true>, dim3(B), dim3(SDF_SAMPLE_THREADS), tail_lds, st, ta);
-            else
-                hipLaunchKernelGGL(opt_tail_kernel<false>, dim3(B), dim3(SDF_SAMPLE_THREADS), tail_lds, st, ta);
-            if (timed) { if (int rc2 = timed_next(&tcur, IHMR_TIMED_OPT_TAIL, st)) return rc2; (void)hipEventDestroy(tcur); }
-            if (pose_stage)
-                lbs_backward_launch(m, true, 2 * B, B, wk.g_verts, wk.g_joints, wk.g_orient, wk.g_pose, wk.g_shape, wk.g_trans, need_mask,
-                                    wk.lbs, st, /*bwd1_done=*/true);
-        } else {
-            int rc = opt_forward(m, m_left, io, wk, B, *w, step, st, need_cam, it == 0 ? first_mode : keep_mode, it == 0 ? lists_first : 1, true, true, static_mask);   // applies the step of iteration it - 1 first
-            if (rc) return rc;
-            if (need_mask)
-                lbs_backward_launch(m, true, 2 * B, B, wk.g_verts, wk.g_joints, wk.g_orient, wk.g_pose, wk.g_shape, wk.g_trans, need_mask,
-                                    wk.lbs, st);
-        }
+        const plan::StepPlan s = plan::plan_step(sg->lr, sgd, it, sg->save_freq);
+        const ParamStep next{sg->param_mask, w->shape_reg, s.step_size, s.bc2_sqrt, s.snap_idx, 0, sgd};
+        if (int rc = run_iteration(c, plan::plan_iter(p, it, sg->n_iters), step, next)) return rc;
         step = next;
     }
-    hipLaunchKernelGGL(opt_adam_kernel, dim3(B), dim3(128), 0, st, *io, wk, B, step);
-    hipLaunchKernelGGL(opt_select_kernel, dim3((B + 63) / 64), dim3(64), 0, st, *io, B, S, *sg);
+    hipLaunchKernelGGL(opt_adam_kernel, dim3(B), dim3(128), 0, c.st, *io, c.wk, B, step);
+    hipLaunchKernelGGL(opt_select_kernel, dim3((B + 63) / 64), dim3(64), 0, c.st, *io, B, plan::snapshot_count(sg->n_iters, sg->save_freq), *sg);
     return (int)hipGetLastError();
 }
 
@@ -657,19 +614,13 @@ extern "C" int ihmr_mlp_forward_select(const ihmr_mano* m, const ihmr_mano* m_le
     if (!m || !io || !w || !workspace || B <= 0 || 2 * B > SDF_MAX_HANDS || mode < 0 || mode > 3 || (mode && !t)) return -1;
     MlpSelect sel;
     memset(&sel, 0, sizeof(sel));
-    // mode 3 (round 6) = mode 2 for a stage that moves neither finger pose nor shape while the workspace still holds v_posed of exactly
-    // these finger poses and shapes (the caller's bookkeeping: ihmr_amd/mlp_model.py): the skinning launch skips both blends
-    // (lbs_skin_kernel MODE REUSE: the stored values are the bits a recomputation gives)
-    const int skin_mode = mode == 3 ? LBS_SKIN_REUSE : LBS_SKIN_FULL;
+    // mode 3 (round 6): the caller's bookkeeping (ihmr_amd/mlp_model.py) says the workspace holds v_posed of these parameters (plan_mlp_eval)
+    const plan::IterPlan q = plan::plan_mlp_eval(mode);
     if (mode == 3) mode = 2;
     if (mode) { if (int rc = mlp_fill_select(sel, t, stage, mode, workspace)) return rc; }
     OptWork wk = opt_carve(io->workspace, B);
     if (mode) { sel.joints_now = wk.joints_raw; sel.acc_joints = mlp_acc_joints(workspace, B); }
-    // The evaluations of one test() call move the hands by a stage's residual at a time: the collision kernels keep their per-voxel
-    // candidate lists from one evaluation to the next (valid while a hand stays within the slack of the pose its lists were built at,
-    // checked per hand and evaluation; rebuilt otherwise) -- started over by the evaluation that opens the batch.  No static-hand
-    // reuse here: a rejected update falls back to parameters the vertex buffers no longer hold.
-    return opt_forward(m, m_left, io, wk, B, *w, kNoStep, (hipStream_t)stream, 0, skin_mode, mode == 1 ? 2 : 1, true, true, 0, mode ? &sel : nullptr);
+    return run_iteration(OptCtx{m, m_left, io, wk, B, w, (hipStream_t)stream, mode ? &sel : nullptr}, q, kNoStep, kNoStep);
 }
 
 // the evaluation of a stage that moved ONLY the camera: one small launch (mlp_camera_select_kernel, refine.h)
@@ -688,11 +639,7 @@ extern "C" int ihmr_mlp_camera_select(const ihmr_opt_io* io, int B, const ihmr_o
 // skeletons + skinning of the parameters in `io` only (no collision term, no losses): the annotation's meshes of the export
 extern "C" int ihmr_opt_forward_verts(const ihmr_mano* m, const ihmr_opt_io* io, int B, void* stream) {
     if (!m || !io || B <= 0) return -1;
-    hipStream_t st = (hipStream_t)stream;
-    OptWork wk = opt_carve(io->workspace, B);
-    hipLaunchKernelGGL(opt_adam_skel_kernel, dim3(B), dim3(384), 0, st, *m, *io, wk, B, kNoStep, sdf_carve(wk.sdf_ws, 2 * B, true).inside_count);
-    lbs_skin_launch<true>(m, LBS_SKIN_FULL, 2 * B, B, io->verts, wk.joints_raw, wk.lbs, st);
-    return (int)hipGetLastError();
+    return run_iteration(OptCtx{m, nullptr, io, opt_carve(io->workspace, B), B, nullptr, (hipStream_t)stream, nullptr}, plan::kForwardVerts, kNoStep, kNoStep);
 }
 
 // ------------------------------------------------------------------------------------------ stage graphs
@@ -764,7 +711,7 @@ extern "C" int ihmr_opt_sdf_stats(const ihmr_mano* m, const ihmr_mano* m_left, c
     ihmr_kernel_timer* keep = g_timer;
     g_timer = nullptr;
     g_collect_stats = 1;
-    int rc = opt_forward(m, m_left, io, wk, B, *w, kNoStep, st);
+    int rc = run_iteration(OptCtx{m, m_left, io, wk, B, w, st, nullptr}, plan::kForwardLosses, kNoStep, kNoStep);
     g_collect_stats = 0;
     g_timer = keep;
     if (rc) return rc;
@@ -955,9 +902,8 @@ extern "C" int ihmr_mlp_train_grad(const ihmr_mano* m, const ihmr_mano* m_left, 
         return -1;
     hipStream_t st = (hipStream_t)stream;
     OptWork wk = opt_carve(io->workspace, B);
-    int rc = opt_forward(m, m_left, io, wk, B, *w, kNoStep, st);
+    int rc = run_iteration(OptCtx{m, m_left, io, wk, B, w, st, nullptr}, plan::kForwardBackward, kNoStep, kNoStep);
     if (rc) return rc;
-    lbs_backward_launch(m, true, 2 * B, B, wk.g_verts, wk.g_joints, wk.g_orient, wk.g_pose, wk.g_shape, wk.g_trans, 15, wk.lbs, st);
     hipLaunchKernelGGL(mlp_train_grad_kernel, dim3(B), dim3(128), 0, st, *io, wk, B, *tw, gt_pose, gt_shape, params_weight, init_shape,
                        trans_weight_mean, grad122, terms5, out_cols, n_out, d_out, ld_out);
     return (int)hipGetLastError();

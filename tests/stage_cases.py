@@ -1,6 +1,6 @@
 """Which parameter subsets of a refinement stage launch something different, and the inputs the stage tests run them on.  Host only.
 
-`ihmr_opt_run_stage` (csrc/ihmr_hip.hip) derives a stage's whole launch plan from `param_mask`.  `plan` restates that derivation so
+`ihmr_opt_run_stage` (csrc/ihmr_hip.hip, csrc/stage_plan.h) derives a stage's whole launch plan from `param_mask`.  `plan` restates that derivation so
 that the tests can pick ONE mask per distinct plan instead of all 255 (`CLASSES`, `REPRESENTATIVES`); `stage_for` and `batch` build
 the stage and the two B = 3 batches every case runs on; `oracle_gradients` is the float64 / float32 oracle gradient of the whole
 loss over all eight parameter blocks at a given state."""
@@ -21,19 +21,18 @@ TAIL_STEP_SKIN = "opt_tail_kernel<true,true>"   # ... + skinning of the next ver
 TAIL_TRANS = "opt_tail_kernel_trans"            # the translation stage's own tail
 
 Plan = namedtuple("Plan", "need_mask need_cam vposed_fixed pose_fixed first_skin later_skin static_mask trans_tail keep_rot pose_stage "
-                          "fused_tail step_tail last_tail")
+                          "fused_tail step_tail last_tail lists_first")
 
 
-def plan(mask):
-    """The launch plan `ihmr_opt_run_stage` derives from `param_mask` (csrc/ihmr_hip.hip, the block from `const int need_mask` to
-    `const int keep_rot` and the tail selection inside its iteration loop), restated for the default switches: static reuse on,
-    translated reuse on (`sdf_no_static_reuse` = 0), fused tail on (`no_fused_tail` = 0, the tail fits the device), generic tail not
-    forced.  `step_tail` is the tail of every iteration but the stage's last, `last_tail` the last one's (`tail_form`).
+def plan(mask, *, no_fused_tail=0, tail_fits=1, sdf_no_static_reuse=0, force_generic_tail=0, keep_lists=0):
+    """The launch plan `ihmr_opt_run_stage` derives from `param_mask` and its switches (csrc/stage_plan.h: `plan_stage`, and the tail
+    selection of `plan_iter`), restated.  The defaults are the product's: static reuse on, translated reuse on (`sdf_no_static_reuse`
+    = 0), fused tail on (`no_fused_tail` = 0, the tail fits the device), generic tail not forced, candidate lists rebuilt by the
+    stage's first iteration.  `step_tail` is the tail of every iteration but the stage's last, `last_tail` the last one's (`tail_form`).
 
-    The C++ selection cannot be compiled on the host, so nothing here is asserted AGAINST the product and nothing asserts the product
-    against this: it only CHOOSES the cases -- one mask per distinct value -- that tests/test_gpu_stage_masks.py then runs against the
-    generic tail forms, the separate launches and the float64 oracle.  A restatement that drifts from the C++ costs coverage, never
-    a false pass."""
+    This restatement CHOOSES the cases -- one mask per distinct value -- that tests/test_gpu_stage_masks.py runs against the generic
+    tail forms, the separate launches and the float64 oracle; tests/test_stage_plan_cpu.py compiles stage_plan.h for the host and
+    compares it with this function field for field, at every mask, switch combination and iteration."""
     pm = int(mask)
     if not 1 <= pm <= 255:
         raise ValueError(f"param_mask {mask!r}: 1 .. 255")
@@ -44,13 +43,13 @@ def plan(mask):
     pose_fixed = (pm & (POSE_R | POSE_L)) == 0
     later_skin = "REUSE" if vposed_fixed else ("KEEP_P" if pose_fixed else "FULL")
     first_skin = "FULL_STORE_P" if (not vposed_fixed and pose_fixed) else "FULL"
-    fused_tail = need_mask != 0
+    fused_tail = need_mask != 0 and not no_fused_tail and bool(tail_fits)
     static_mask = (0 if pm & (ORIENT_R | POSE_R | SHAPE_R) else 1) | (0 if pm & (ORIENT_L | POSE_L | SHAPE_L | TRANS | SHAPE_R) else 2)
-    if (pm & TRANS) and not (pm & (ORIENT_L | POSE_L | SHAPE_L | SHAPE_R)):
+    if (pm & TRANS) and not (pm & (ORIENT_L | POSE_L | SHAPE_L | SHAPE_R)) and sdf_no_static_reuse == 0:
         static_mask |= 2 | (2 << 2)           # the left hand only translates: static in its own frame, with a moving box
     pose_stage = (need_mask & 2) != 0
-    trans_tail = vposed_fixed and need_mask == 8
-    keep_rot = 0 if (need_mask & 7) == 0 else ((0 if pm & (ORIENT_R | POSE_R) else 1) | (0 if pm & (ORIENT_L | POSE_L) else 2))
+    trans_tail = vposed_fixed and need_mask == 8 and not force_generic_tail
+    keep_rot = 0 if ((need_mask & 7) == 0 or force_generic_tail) else ((0 if pm & (ORIENT_R | POSE_R) else 1) | (0 if pm & (ORIENT_L | POSE_L) else 2))
     if not fused_tail:
         step_tail = last_tail = TAIL_SEPARATE
     else:
@@ -58,14 +57,14 @@ def plan(mask):
         last_tail = TAIL_PLAIN
     # (the skinning launch of a later iteration is the tail's own fourth phase in the forms that skin)
     return Plan(need_mask, need_cam, vposed_fixed, pose_fixed, first_skin, later_skin, static_mask, trans_tail, keep_rot, pose_stage,
-                fused_tail, step_tail, last_tail)
+                fused_tail, step_tail, last_tail, "KEEP" if keep_lists else "REBUILD")
 
 
-def tail_form(mask, it, n):
+def tail_form(mask, it, n, **switches):
     """The tail of iteration `it` of an `n`-iteration stage."""
     if not 0 <= it < n:
         raise ValueError("0 <= it < n")
-    p = plan(mask)
+    p = plan(mask, **switches)
     return p.step_tail if it + 1 < n else p.last_tail
 
 
