@@ -1,6 +1,7 @@
 // Evaluation metrics on the device: the four numbers the reference prints after a run (optimize.py:98-102) --
 // mpjpe_3d, inter_mpjpe_3d, collision_ave, collision_max -- as per-sample partial results that the host adds up
-// in float64 (and all-reduces over ranks, ihmr_amd/dist.py).
+// in float64 (and all-reduces over ranks, ihmr_amd/dist.py) -- and, at the end of this file, the Procrustes-aligned errors
+// (PA-MPJPE / PA-MPVPE, utils/metric_utils.py:59-104) that the reference carries as calc_transform.
 //
 // Reference: utils/metric_utils.py:23-38 (get_single_joints_error: per-hand MPJPE with the root subtraction
 // applied CUMULATIVELY to the same copies), :107-117 (calc_transform_no_rot: per-axis mean / std alignment),
@@ -8,6 +9,7 @@
 // mean / max of the 1556 per-vertex depths x 1000, over samples whose hand_type is 'interacting').
 #pragma once
 #include "ihmr_common.h"
+#include "eval_pure.h"
 
 // grid = B, block = 64: lane j < 42 owns joint j.  out (B,6) doubles:
 //   [0] sum of per-joint errors, [1] number of them, [2] sum of aligned ("inter") errors, [3] number of them,
@@ -136,4 +138,152 @@ __global__ __launch_bounds__(256) void eval_mpvpe_kernel(const float* __restrict
     if (lane == 0) part[wave][0] = s;
     __syncthreads();
     if (tid == 0) { o[0] = ((double)part[0][0] + (double)part[1][0]) + ((double)part[2][0] + (double)part[3][0]); o[1] = (double)NV; }
+}
+
+// ------------------------------------------------------------------------------------------ Procrustes-aligned errors (PA-MPJPE / PA-MPVPE)
+// utils/metric_utils.py:59-104 (calc_transform) and :120-143 (get_single_pa_inter_joints_error, use_rot=True), read with the points
+// in rows; the arithmetic and the set rules are csrc/eval_pure.h.  Inputs float32, every operation float64, no atomics; every sum has
+// one fixed order (lane-strided partials, xor butterfly over the wave, waves in index order), so a sample's result does not depend on
+// its place in the batch.
+__device__ __forceinline__ double wave_reduce_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// grid = B, block = 64: lane j < 42 owns joint j.  Three sets per sample: 0 = all valid joints (the reference's call), 1 = the valid
+// joints of the right hand (0..20), 2 = those of the left hand (21..41).  out (B,3,2) doubles [sum of errors, count];
+// point_err (B,3,42) doubles or NULL: the aligned error of a set's member, 0 for every other joint and for a set left out.
+__global__ __launch_bounds__(64) void eval_pa_joints_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                            const float* __restrict__ scale, int B, double* __restrict__ out,
+                                                            double* __restrict__ point_err) {
+    const int b = blockIdx.x, j = threadIdx.x;
+    const bool act = j < 42;
+    double p[3] = {0.0, 0.0, 0.0}, g[3] = {0.0, 0.0, 0.0}, w = 0.0;
+    if (act) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { p[k] = (double)pred[((size_t)b * 42 + j) * 3 + k]; g[k] = (double)gt[((size_t)b * 42 + j) * 4 + k]; }
+        w = (double)gt[((size_t)b * 42 + j) * 4 + 3];
+    }
+    const double sc = scale ? (double)scale[b] : 1.0;
+#pragma nounroll
+    for (int s = 0; s < 3; ++s) {
+        const int lo = s == 2 ? 21 : 0, hi = s == 1 ? 21 : 42;
+        const bool in_set = act && j >= lo && j < hi;
+        const bool member = in_set && w > 0.0;
+        const double wsum = wave_reduce_sum_f64(in_set ? w : 0.0);
+        const double n = wave_reduce_sum_f64(member ? 1.0 : 0.0);
+        double err = 0.0;
+        bool kept = false;
+        if (wsum >= EVP_MIN_WEIGHT_SUM && n > 0.0) {          // uniform over the wave
+            double m1[3], m2[3], x1[3], x2[3], M[3][3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                m1[k] = wave_reduce_sum_f64(member ? p[k] : 0.0) / n;
+                m2[k] = wave_reduce_sum_f64(member ? g[k] : 0.0) / n;
+                x1[k] = member ? p[k] - m1[k] : 0.0;
+                x2[k] = member ? g[k] - m2[k] : 0.0;
+            }
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) M[a][c] = wave_reduce_sum_f64(x1[a] * x2[c]);
+            const double var1 = wave_reduce_sum_f64((x1[0] * x1[0] + x1[1] * x1[1]) + x1[2] * x1[2]);
+            if (var1 > 0.0) {
+                kept = true;
+                const evp_transform T = procrustes_from_moments(n, m1, m2, M, var1);
+                if (member) err = evp_aligned_error(T, p, g) / sc;
+            }
+        }
+        const double esum = wave_reduce_sum_f64(err);
+        if (point_err && act) point_err[((size_t)b * 3 + s) * 42 + j] = err;
+        if (j == 0) {
+            double* o = out + ((size_t)b * 3 + s) * 2;
+            o[0] = kept ? esum : 0.0;
+            o[1] = kept ? n : 0.0;
+        }
+    }
+}
+
+// grid = (B, 2), block = 256: one hand's 778 vertices, all valid; the hand counts when mano_params_weight[b][h] > 0.  Three passes over
+// the mesh: means, centred moments, errors.  out (B,2,2) doubles [sum of errors, count]; point_err (B,2,778) doubles or NULL.
+__global__ __launch_bounds__(256) void eval_pa_verts_kernel(const float* __restrict__ pred_r, const float* __restrict__ pred_l,
+                                                            const float* __restrict__ gt_r, const float* __restrict__ gt_l,
+                                                            const float* __restrict__ params_weight, const float* __restrict__ scale,
+                                                            int B, double* __restrict__ out, double* __restrict__ point_err) {
+    __shared__ double part[4][10];
+    const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
+    double* o = out + ((size_t)b * 2 + h) * 2;
+    double* pe = point_err ? point_err + ((size_t)b * 2 + h) * NV : nullptr;
+    const float* P = (h ? pred_l : pred_r) + (size_t)b * NV3;
+    const float* G = (h ? gt_l : gt_r) + (size_t)b * NV3;
+    bool kept = params_weight[b * 2 + h] > 0.f;      // uniform over the block
+    evp_transform T;
+    if (kept) {
+        double acc[10];
+#pragma unroll
+        for (int k = 0; k < 10; ++k) acc[k] = 0.0;
+        for (int v = tid; v < NV; v += 256) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { acc[k] += (double)P[3 * v + k]; acc[3 + k] += (double)G[3 * v + k]; }
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            const double s = wave_reduce_sum_f64(acc[k]);
+            if (lane == 0) part[wave][k] = s;
+        }
+        __syncthreads();
+        double m1[3], m2[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            m1[k] = (((part[0][k] + part[1][k]) + part[2][k]) + part[3][k]) / (double)NV;
+            m2[k] = (((part[0][3 + k] + part[1][3 + k]) + part[2][3 + k]) + part[3][3 + k]) / (double)NV;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 10; ++k) acc[k] = 0.0;
+        for (int v = tid; v < NV; v += 256) {
+            double x1[3], x2[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { x1[k] = (double)P[3 * v + k] - m1[k]; x2[k] = (double)G[3 * v + k] - m2[k]; }
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[3 * a + c] += x1[a] * x2[c];
+            acc[9] += (x1[0] * x1[0] + x1[1] * x1[1]) + x1[2] * x1[2];
+        }
+#pragma unroll
+        for (int k = 0; k < 10; ++k) {
+            const double s = wave_reduce_sum_f64(acc[k]);
+            if (lane == 0) part[wave][k] = s;
+        }
+        __syncthreads();
+        double M[3][3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) M[a][c] = ((part[0][3 * a + c] + part[1][3 * a + c]) + part[2][3 * a + c]) + part[3][3 * a + c];
+        const double var1 = ((part[0][9] + part[1][9]) + part[2][9]) + part[3][9];
+        __syncthreads();
+        kept = var1 > 0.0;
+        if (kept) T = procrustes_from_moments((double)NV, m1, m2, M, var1);
+    }
+    if (!kept) {
+        if (pe) for (int v = tid; v < NV; v += 256) pe[v] = 0.0;
+        if (tid == 0) { o[0] = 0.0; o[1] = 0.0; }
+        return;
+    }
+    const double sc = scale ? (double)scale[b] : 1.0;
+    double esum = 0.0;
+    for (int v = tid; v < NV; v += 256) {
+        const double p[3] = {(double)P[3 * v], (double)P[3 * v + 1], (double)P[3 * v + 2]};
+        const double g[3] = {(double)G[3 * v], (double)G[3 * v + 1], (double)G[3 * v + 2]};
+        const double e = evp_aligned_error(T, p, g) / sc;
+        esum += e;
+        if (pe) pe[v] = e;
+    }
+    const double s = wave_reduce_sum_f64(esum);
+    if (lane == 0) part[wave][0] = s;
+    __syncthreads();
+    if (tid == 0) { o[0] = ((part[0][0] + part[1][0]) + part[2][0]) + part[3][0]; o[1] = (double)NV; }
 }

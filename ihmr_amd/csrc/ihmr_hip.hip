@@ -891,6 +891,23 @@ extern "C" int ihmr_eval_mpvpe(const float* pred_right, const float* pred_left, 
     return (int)hipGetLastError();
 }
 
+extern "C" int ihmr_eval_pa_joints(const float* pred_joints_3d, const float* gt_joints_3d, const float* sample_scale, int B, double* out,
+                                   double* point_err, void* stream) {
+    if (!pred_joints_3d || !gt_joints_3d || !out || B <= 0) return -1;
+    hipLaunchKernelGGL(eval_pa_joints_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, pred_joints_3d, gt_joints_3d, sample_scale, B,
+                       out, point_err);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ihmr_eval_pa_verts(const float* pred_right, const float* pred_left, const float* gt_right, const float* gt_left,
+                                  const float* mano_params_weight, const float* sample_scale, int B, double* out, double* point_err,
+                                  void* stream) {
+    if (!pred_right || !pred_left || !gt_right || !gt_left || !mano_params_weight || !out || B <= 0) return -1;
+    hipLaunchKernelGGL(eval_pa_verts_kernel, dim3(B, 2), dim3(256), 0, (hipStream_t)stream, pred_right, pred_left, gt_right, gt_left,
+                       mano_params_weight, sample_scale, B, out, point_err);
+    return (int)hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------ IHMR-MLP training step
 extern "C" int ihmr_mlp_train_grad(const ihmr_mano* m, const ihmr_mano* m_left, const ihmr_opt_io* io, int B,
                                    const ihmr_opt_weights* w, const ihmr_train_weights* tw, const float* gt_pose,

@@ -44,13 +44,80 @@ def calc_transform_no_rot(S1, S2):
     return (S1 - m1) / s1 * s2 + m2
 
 
-def get_single_pa_inter_joints_error(pred, gt, joints_valid, scale_factor):
-    """metric_utils.py:120-143 with use_rot=False."""
+def calc_transform(S1, S2):
+    """metric_utils.py:59-104 -- similarity Procrustes alignment of S1 onto S2, restated with the reference's dtype behaviour: the
+    covariance and the SVD run in the dtype of the inputs (float32 arrays stay float32; only the sign matrix is float64, which lifts
+    the rotation and everything after it to float64), and, like the reference, the inputs are transposed to coordinates x points
+    ONLY when ``S1.shape[0]`` is neither 3 nor 2.  A set of exactly 3 or exactly 2 points, shaped (3,3) or (2,3), is therefore read
+    as coordinates x points and a different problem is solved (for (2,3): in two dimensions).  :func:`procrustes_align` is the
+    points-in-rows form that the Evaluator's PA metrics are defined by."""
+    transposed = S1.shape[0] != 3 and S1.shape[0] != 2
+    if transposed:
+        S1, S2 = S1.T, S2.T
+    assert S2.shape[1] == S1.shape[1]
+    mu1, mu2 = S1.mean(axis=1, keepdims=True), S2.mean(axis=1, keepdims=True)
+    X1, X2 = S1 - mu1, S2 - mu2
+    var1 = np.sum(X1 ** 2)
+    K = X1.dot(X2.T)
+    U, _, Vh = np.linalg.svd(K)
+    V = Vh.T
+    Z = np.eye(U.shape[0])
+    Z[-1, -1] *= np.sign(np.linalg.det(U.dot(V.T)))
+    R = V.dot(Z.dot(U.T))
+    scale = np.trace(R.dot(K)) / var1
+    t = mu2 - scale * (R.dot(mu1))
+    S1_hat = scale * R.dot(S1) + t
+    return S1_hat.T if transposed else S1_hat
+
+
+def get_single_pa_inter_joints_error(pred, gt, joints_valid, scale_factor, use_rot=False):
+    """metric_utils.py:120-143; ``use_rot=True`` aligns with :func:`calc_transform` (the reference's reading of 3 and 2 valid
+    joints included), the default with :func:`calc_transform_no_rot`."""
     v = joints_valid[:, 0] if joints_valid.ndim == 2 else joints_valid
     if np.sum(v) < 2.0:
         return []
     p, g = pred[v > 0, :3], gt[v > 0, :3]
-    return (np.linalg.norm(calc_transform_no_rot(p.copy(), g.copy()) - g, axis=1) / scale_factor).tolist()
+    transform = calc_transform if use_rot else calc_transform_no_rot
+    return (np.linalg.norm(transform(p.copy(), g.copy()) - g, axis=1) / scale_factor).tolist()
+
+
+PA_MIN_WEIGHT_SUM = 2.0        # metric_utils.py:131: the SUM of the weights, not the number of valid points
+
+
+def procrustes_align(S1, S2):
+    """S1 (n,3) aligned onto S2 (n,3) by the similarity transform (proper rotation, scale, translation) of least squared error:
+    always points in rows, always float64.  For n not in {2, 3} this is :func:`calc_transform` on float64 inputs; 2 points are
+    mapped onto their targets exactly.  Returns None when all points of S1 coincide (``var1 == 0``): the reference divides by zero
+    there, this build leaves the set out (a deviation, so that one sample cannot turn a float64 sum into NaN).  The test is exact
+    for float32 inputs, which is what the models export: a float64 sum of equal float32 values is exact, so is their mean."""
+    S1, S2 = np.asarray(S1, np.float64), np.asarray(S2, np.float64)
+    assert S1.ndim == 2 and S1.shape[1] == 3 and S1.shape == S2.shape and len(S1) > 0
+    m1, m2 = S1.mean(axis=0), S2.mean(axis=0)
+    X1, X2 = S1 - m1, S2 - m2
+    var1 = np.sum(X1 ** 2)
+    if var1 == 0.0:
+        return None
+    K = X1.T @ X2                                   # K[a][b] = sum x1_a x2_b
+    U, _, Vh = np.linalg.svd(K)                     # full 3 x 3 factors: the basis of a rank-deficient K is completed
+    Z = np.eye(3)
+    Z[2, 2] = np.sign(np.linalg.det(U @ Vh))
+    R = Vh.T @ Z @ U.T
+    scale = np.trace(R @ K) / var1
+    return scale * (S1 @ R.T) + (m2 - scale * (R @ m1))
+
+
+def get_single_pa_error(pred, gt, weights, scale_factor):
+    """Aligned per-point errors of ONE set (the valid points of ``pred`` / ``gt`` (n,3)), by the set rules shared with the device
+    (``ihmr_eval_pa_joints`` / ``ihmr_eval_pa_verts``): a point is valid when its weight is > 0; the set is left out ([]) when the
+    sum of its weights is < 2.0 or when :func:`procrustes_align` refuses it."""
+    w = np.asarray(weights, np.float64).reshape(-1)
+    if np.sum(w) < PA_MIN_WEIGHT_SUM or not (w > 0).any():
+        return []
+    g = np.asarray(gt, np.float64)[w > 0, :3]
+    aligned = procrustes_align(np.asarray(pred)[w > 0, :3], g)
+    if aligned is None:
+        return []
+    return (np.linalg.norm(aligned - g, axis=1) / scale_factor).tolist()
 
 
 def get_single_verts_error(pred_verts, gt_verts, root_weights, scale_factor):
@@ -78,7 +145,8 @@ def write_image_bgr(path, img):
 
 
 class Evaluator:
-    def __init__(self, mano_models=None, data_list=None, image_root="", inputSize=224):
+    def __init__(self, mano_models=None, data_list=None, image_root="", inputSize=224, pa_metrics=False):
+        self.pa_metrics = pa_metrics    # records carry the Procrustes-aligned errors too (off: records and files as before)
         self.inputSize = inputSize      # evaluator.py:27 (model.inputSize): the visualisation renders at twice this size by default
         self.left_hand_faces = None if mano_models is None else mano_models["left"].faces
         self.right_hand_faces = None if mano_models is None else mano_models["right"].faces
@@ -93,11 +161,53 @@ class Evaluator:
         self.pred_results = []
         self._device_parts = []        # (B,6) float64 device tensors + keep masks, summed lazily
         self._device_vert_parts = []   # (B,2) float64 [sum of per-vertex errors, count]
+        self._device_pa_parts = []     # (B,4) float64 [sum of set 0, count, sum of the per-hand sets, count]
+        self._device_pa_vert_parts = []   # (B,2) float64 [sum of aligned per-vertex errors, count]
 
     def clear(self):
         self.pred_results = []
         self._device_parts = []
         self._device_vert_parts = []
+        self._device_pa_parts = []
+        self._device_pa_vert_parts = []
+
+    def update_device_pa(self, pred_joints_3d, gt_joints_3d, keep=None, scale=None):
+        """Procrustes-aligned joint errors of one batch from device tensors (``ihmr_eval_pa_joints``): pred_joints_3d (B,42,3),
+        gt_joints_3d (B,42,4); ``keep`` and ``scale`` as in :meth:`update_device`.  Accumulates lazily, see :meth:`pa_metric_sums`."""
+        import torch
+
+        from . import hip
+        hip.require_gpu()
+        B, dev = pred_joints_3d.shape[0], pred_joints_3d.device
+        f = lambda t: t.detach().to(dev, torch.float32).contiguous()
+        p, g = f(pred_joints_3d), f(gt_joints_3d)
+        sc = None if scale is None else f(scale)
+        out = torch.empty(B, 3, 2, device=dev, dtype=torch.float64)
+        hip.check(hip.lib().ihmr_eval_pa_joints(p.data_ptr(), g.data_ptr(), None if sc is None else sc.data_ptr(), B, out.data_ptr(),
+                                                None, hip.stream_ptr()), "ihmr_eval_pa_joints")
+        part = torch.cat([out[:, 0], out[:, 1] + out[:, 2]], dim=1)
+        if keep is not None:
+            part = part * keep.to(dev, torch.float64)[:, None]
+        self._device_pa_parts.append(part)
+
+    def update_device_pa_verts(self, pred_right, pred_left, gt_right, gt_left, mano_params_weight, keep=None, scale=None):
+        """PA-MPVPE partial sums of one batch from device tensors (``ihmr_eval_pa_verts``); arguments as :meth:`update_device_verts`."""
+        import torch
+
+        from . import hip
+        hip.require_gpu()
+        B, dev = pred_right.shape[0], pred_right.device
+        f = lambda t: t.detach().to(dev, torch.float32).contiguous()
+        pr, pl, gr, gl, w = f(pred_right), f(pred_left), f(gt_right), f(gt_left), f(mano_params_weight)
+        sc = None if scale is None else f(scale)
+        out = torch.empty(B, 2, 2, device=dev, dtype=torch.float64)
+        hip.check(hip.lib().ihmr_eval_pa_verts(pr.data_ptr(), pl.data_ptr(), gr.data_ptr(), gl.data_ptr(), w.data_ptr(),
+                                               None if sc is None else sc.data_ptr(), B, out.data_ptr(), None, hip.stream_ptr()),
+                  "ihmr_eval_pa_verts")
+        out = out[:, 0] + out[:, 1]
+        if keep is not None:
+            out = out * keep.to(dev, torch.float64)[:, None]
+        self._device_pa_vert_parts.append(out)
 
     def update_device(self, pred_joints_3d, gt_joints_3d, collision_loss_origin_scale, keep=None, interacting=None, scale=None):
         """Metrics of one batch straight from device tensors: pred_joints_3d (B,42,3), gt_joints_3d (B,42,4),
@@ -190,6 +300,18 @@ class Evaluator:
                         single["v3d_error"] += get_single_verts_error(pred_results[f"pred_{side}_hand_verts"][i],
                                                                       pred_results[f"gt_{side}_hand_verts"][i],
                                                                       self.root_weights[h], single["scale"])
+            if getattr(self, "pa_metrics", False):
+                p = single["pred_joints_3d"]
+                single["pa_inter_j3d_error"] = get_single_pa_error(p, gt[:, :3], gt[:, 3], single["scale"])
+                single["pa_j3d_error"] = (get_single_pa_error(p[:21], gt[:21, :3], gt[:21, 3], single["scale"])
+                                          + get_single_pa_error(p[21:], gt[21:, :3], gt[21:, 3], single["scale"]))
+                if "gt_right_hand_verts" in pred_results and self.root_weights is not None:
+                    single["pa_v3d_error"] = []
+                    for h, side in enumerate(("right", "left")):
+                        if pred_results["mano_params_weight"][i][h] > 0:
+                            single["pa_v3d_error"] += get_single_pa_error(pred_results[f"pred_{side}_hand_verts"][i],
+                                                                          pred_results[f"gt_{side}_hand_verts"][i],
+                                                                          np.ones(len(pred_results[f"pred_{side}_hand_verts"][i])), single["scale"])
             if "do_flip" in pred_results and pred_results["do_flip"][i]:
                 self._flip_back_data(single)
             self.pred_results.append(single)
@@ -252,6 +374,31 @@ class Evaluator:
             sums[7:9] = sums[7:9] + torch.cat(self._device_vert_parts, dim=0).sum(dim=0).cpu().numpy()
         return sums
 
+    def pa_metric_sums(self):
+        """[sum PA error over all valid joints, n, sum per-hand PA error, n, sum PA vertex error, n] (float64, additive over ranks):
+        the records of an ``Evaluator(pa_metrics=True)`` plus what :meth:`update_device_pa` / :meth:`update_device_pa_verts` left on
+        the device."""
+        f64 = lambda x: float(np.sum(np.asarray(x, dtype=np.float64)))
+        cols = [[x for p in self.pred_results for x in p.get(k, [])] for k in ("pa_inter_j3d_error", "pa_j3d_error", "pa_v3d_error")]
+        sums = np.array([v for c in cols for v in (f64(c), len(c))], dtype=np.float64)
+        if getattr(self, "_device_pa_parts", None):
+            import torch
+            sums[:4] = sums[:4] + torch.cat(self._device_pa_parts, dim=0).sum(dim=0).cpu().numpy()
+        if getattr(self, "_device_pa_vert_parts", None):
+            import torch
+            sums[4:6] = sums[4:6] + torch.cat(self._device_pa_vert_parts, dim=0).sum(dim=0).cpu().numpy()
+        return sums
+
+    @staticmethod
+    def pa_metrics_from_sums(s):
+        """``pa_inter_mpjpe_3d`` (one alignment over all valid joints of both hands, the reference's ``use_rot=True`` call),
+        ``pa_mpjpe_3d`` (one alignment per hand) and, where aligned vertex errors were counted, ``pa_mpvpe_3d``."""
+        d = lambda a, b: float(a / b) if b > 0 else float("nan")
+        out = dict(pa_inter_mpjpe_3d=d(s[0], s[1]), pa_mpjpe_3d=d(s[2], s[3]))
+        if s[5] > 0:
+            out["pa_mpvpe_3d"] = d(s[4], s[5])
+        return out
+
     @staticmethod
     def metrics_from_sums(s):
         d = lambda a, b: float(a / b) if b > 0 else float("nan")
@@ -270,6 +417,12 @@ class Evaluator:
     def collision_max(self): return self.metrics_from_sums(self.metric_sums())["collision_max"]
     @property
     def mpvpe_3d(self): return self.metrics_from_sums(self.metric_sums()).get("mpvpe_3d", float("nan"))
+    @property
+    def pa_inter_mpjpe_3d(self): return self.pa_metrics_from_sums(self.pa_metric_sums())["pa_inter_mpjpe_3d"]
+    @property
+    def pa_mpjpe_3d(self): return self.pa_metrics_from_sums(self.pa_metric_sums())["pa_mpjpe_3d"]
+    @property
+    def pa_mpvpe_3d(self): return self.pa_metrics_from_sums(self.pa_metric_sums()).get("pa_mpvpe_3d", float("nan"))
 
     # ------------------------------------------------------------------------------------------ visualisation (evaluator.py:184-275)
     def _build_dirs(self, res_dir):

@@ -34,7 +34,7 @@ EXPORTED_SYMBOLS = [
     "ihmr_mano_lbs_bwd",
     "ihmr_sdf_workspace_bytes", "ihmr_sdf_collision", "ihmr_sdf_collision_ex", "ihmr_sdf_dense_grid", "ihmr_opt_workspace_bytes",
     "ihmr_opt_run_stage", "ihmr_opt_forward_losses", "ihmr_opt_sdf_stats", "ihmr_opt_sdf_counters", "ihmr_opt_sdf_inside_bits", "ihmr_opt_stage_graph_create",
-    "ihmr_opt_forward_graph_create", "ihmr_graph_launch", "ihmr_graph_destroy", "ihmr_opt_set_params", "ihmr_eval_metrics", "ihmr_eval_mpvpe", "ihmr_conv_igemm", "ihmr_maxpool3x3s2",
+    "ihmr_opt_forward_graph_create", "ihmr_graph_launch", "ihmr_graph_destroy", "ihmr_opt_set_params", "ihmr_eval_metrics", "ihmr_eval_mpvpe", "ihmr_eval_pa_joints", "ihmr_eval_pa_verts", "ihmr_conv_igemm", "ihmr_maxpool3x3s2",
     "ihmr_avgpool_relu", "ihmr_preprocess_images", "ihmr_mlp_train_grad", "ihmr_transpose", "ihmr_relu_backward", "ihmr_colsum",
     "ihmr_adam_step", "ihmr_bn_workspace_bytes", "ihmr_bn_train_forward", "ihmr_bn_train_backward", "ihmr_conv_wgrad",
     "ihmr_dilate2", "ihmr_interleave2", "ihmr_pack_dgrad_weight", "ihmr_maxpool3x3s2_backward", "ihmr_avgpool_relu_backward", "ihmr_set_kernel_timer", "ihmr_flush_kernel_timer",
@@ -279,6 +279,11 @@ def lib():
         L.ihmr_opt_forward_verts.argtypes = [vp, C.POINTER(OptIO), i, vp]
         L.ihmr_eval_metrics.argtypes = [vp, vp, vp, vp, vp, i, vp, vp]
         L.ihmr_eval_mpvpe.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, vp, vp]
+        # a library named with IHMR_HIP_LIBRARY may be an older build (A/B runs against the parent commit): it loads, and a call of an
+        # entry point it lacks raises AttributeError
+        for name, sig in (("ihmr_eval_pa_joints", [vp, vp, vp, i, vp, vp, vp]), ("ihmr_eval_pa_verts", [vp, vp, vp, vp, vp, vp, i, vp, vp, vp])):
+            if hasattr(L, name):
+                getattr(L, name).argtypes = sig
         L.ihmr_graph_destroy.argtypes = [vp]
         L.ihmr_conv_igemm.argtypes = [vp, vp, vp, vp, vp] + [i] * 16 + [vp, C.c_size_t, vp]
         L.ihmr_maxpool3x3s2.argtypes = [vp, vp, i, i, i, i, i, i, vp]

@@ -37,6 +37,9 @@ def main(argv=None):
     ap.add_argument("--host_eval", action="store_true",
                     help="evaluate with the host (numpy) Evaluator on get_pred_result() exports, as the reference does; "
                          "default: metrics on the device (ihmr_eval_metrics), no export")
+    ap.add_argument("--pa_metrics", action="store_true",
+                    help="also report the Procrustes-aligned joint errors pa_inter_mpjpe_3d (one alignment over both hands) and "
+                         "pa_mpjpe_3d (one per hand): on the device (ihmr_eval_pa_joints), from the records under --host_eval")
     ap.add_argument("--streams", type=int, default=1,
                     help="model instances driven side by side on their own HIP streams (2 x --fuse_batches 8 saturates one MI355X; "
                          "more than 4 need GPU_MAX_HW_QUEUES raised in the environment)")
@@ -58,7 +61,7 @@ def main(argv=None):
     singles = [model] + [None] * (S - 1)                                      # remainder of fewer than G batches: batch by batch
     main_stream = torch.cuda.current_stream()
     streams = [torch.cuda.Stream() for _ in range(S)] if S > 1 else [main_stream]
-    evaluator = Evaluator(model.mano_models)
+    evaluator = Evaluator(model.mano_models, pa_metrics=args.pa_metrics)
     fwd = lambda p, s, t: two_hand.forward_from_packed(model.mano_models["right"], p.cuda(), s.cuda(), t.cuda())[2]
 
     idx, is_pad = D.shard_indices(args.num_samples, args.batchSize, rank, world)
@@ -106,19 +109,26 @@ def main(argv=None):
                 else:
                     evaluator.update_device(mdl.pred_joints_3d, mdl.buf["gt_joints_3d"], mdl.collision_loss_origin_scale,
                                             keep=torch.from_numpy(~pad))
+                    if args.pa_metrics:
+                        evaluator.update_device_pa(mdl.pred_joints_3d, mdl.buf["gt_joints_3d"], keep=torch.from_numpy(~pad))
         for _, st, *_ in jobs:
             main_stream.wait_stream(st)                 # the next round's data generation reuses the instances' MANO handles
     torch.cuda.synchronize()
-    sums = D.reduce_metrics(evaluator.metric_sums())
+    base = evaluator.metric_sums()
+    n_base = len(base)
+    # with --pa_metrics both metric vectors travel in the one all-reduce
+    sums = D.reduce_metrics(np.concatenate([base, evaluator.pa_metric_sums()]) if args.pa_metrics else base)
     elapsed = time.time() - t0
+    m = Evaluator.metrics_from_sums(sums[:n_base])
+    if args.pa_metrics:
+        m.update(Evaluator.pa_metrics_from_sums(sums[n_base:]))
     if rank == 0:
-        m = Evaluator.metrics_from_sums(sums)
-        for k in ("mpjpe_3d", "inter_mpjpe_3d", "collision_ave", "collision_max"):
+        for k in ("mpjpe_3d", "inter_mpjpe_3d", "collision_ave", "collision_max") + (("pa_inter_mpjpe_3d", "pa_mpjpe_3d") if args.pa_metrics else ()):
             print(f"{k} : {m[k]:.3f} (optimize)")
         print(json.dumps(dict(num_samples=args.num_samples, world=world, seconds=elapsed, **m)))
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
-    return Evaluator.metrics_from_sums(sums)
+    return m
 
 
 if __name__ == "__main__":

@@ -307,6 +307,25 @@ int ihmr_eval_mpvpe(const float* pred_right, const float* pred_left, const float
                     const float* root_weights, const float* mano_params_weight, const float* sample_scale, int B,
                     double* out4, void* stream);
 
+/* Procrustes-aligned errors: PA-MPJPE / PA-MPVPE, the error that is left after the similarity transform (rotation, scale,
+ * translation) that best maps the predicted points onto the target (utils/metric_utils.py:59-104 calc_transform, :120-143
+ * get_single_pa_inter_joints_error with use_rot=True), with the points in rows.  Inputs float32, arithmetic float64 in a fixed
+ * order (csrc/eval_pure.h: Horn's quaternion form, cyclic Jacobi).  A point is valid when its weight is > 0; a set is LEFT OUT
+ * ([0, 0], zero rows of point_err) when the sum of its weights is < 2.0 (the reference's rule) or when all its valid predicted
+ * points coincide (the reference divides by zero there; this build leaves the set out).  The reference reads a set of exactly 3 or
+ * 2 valid points as coordinates x points (:64); these entry points always read points in rows.
+ *   ihmr_eval_pa_joints  pred_joints_3d (B,42,3), gt_joints_3d (B,42,4) [xyz, weight]; three sets per sample: all valid joints (the
+ *                        reference's call), the valid joints of the right hand (0-20), those of the left hand (21-41).
+ *                        out (B,3,2) float64 [sum of errors, count]; point_err (B,3,42) float64 or NULL.
+ *   ihmr_eval_pa_verts   the four meshes (B,778,3), all vertices valid; a hand counts when mano_params_weight (B,2) is > 0.
+ *                        out (B,2,2) float64 [sum, count] for right, left; point_err (B,2,778) float64 or NULL.
+ * sample_scale (B) or NULL (= 1) divides every error.  point_err receives 0 for an invalid point and for a point of a set left out.
+ * -1 for a NULL required pointer or B <= 0 (nothing is launched); no allocation, no synchronisation. */
+int ihmr_eval_pa_joints(const float* pred_joints_3d, const float* gt_joints_3d, const float* sample_scale, int B, double* out,
+                        double* point_err, void* stream);
+int ihmr_eval_pa_verts(const float* pred_right, const float* pred_left, const float* gt_right, const float* gt_left,
+                       const float* mano_params_weight, const float* sample_scale, int B, double* out, double* point_err, void* stream);
+
 /* ------------------------------------------------------------------ packed transfers (round 5)
  * MLPModel.set_input (models/mlp_model.py:120-170) and get_pred_result (:702-719) move 17 + 13 small tensors one copy at a time; one
  * launch does a whole table of them.  A segment = a 2-D strided copy of 32-bit words: dst[r * dst_ld + c] = src[r * src_ld + c] for
