@@ -70,6 +70,98 @@ static inline LbsWork lbs_carve(void* ws, int N) {
     return w;
 }
 
+// ------------------------------------------------------------------------------------- shared pieces
+// The one definition of each sum that several kernels must form in the same order to give the same bits.
+//
+// One joint's share of a vertex's blended transform T = sum_j w_j A_j: T[4q + c] = fma(w, A_j[4q + c], T[4q + c]), the joint's row Aj
+// (12 floats, 16-byte aligned, LDS) read as three float4.  COLS = 3: the rotation columns only (T[4q + 3] is left alone), COLS = 4: with
+// the translation column.  Callers add the joints in index order.
+template <int COLS>
+__device__ __forceinline__ void lbs_T_add(float (&T)[12], float w, const float* Aj) {
+    const float4* A4 = reinterpret_cast<const float4*>(Aj);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const float4 a = A4[q];
+        T[4 * q] = __builtin_fmaf(w, a.x, T[4 * q]);
+        T[4 * q + 1] = __builtin_fmaf(w, a.y, T[4 * q + 1]);
+        T[4 * q + 2] = __builtin_fmaf(w, a.z, T[4 * q + 2]);
+        if (COLS == 4) T[4 * q + 3] = __builtin_fmaf(w, a.w, T[4 * q + 3]);
+    }
+}
+// T from zero over the vertex's (up to) four non-zero weights, in slot order (= joint order: the dense sum without its zero terms,
+// fma(0, a, T) == T); w4 / j4 = the vertex's entries of ihmr_mano::w4_w / w4_j, sA = the hand's 16 skinning matrices in LDS.
+template <int COLS>
+__device__ __forceinline__ void lbs_T_sparse4(float (&T)[12], const float* sA, float4 w4, uint32_t j4) {
+    const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+    for (int e = 0; e < 12; ++e) T[e] = 0.f;
+#pragma unroll
+    for (int sI = 0; sI < 4; ++sI) lbs_T_add<COLS>(T, wv[sI], sA + 12 * (int)((j4 >> (8 * sI)) & 0xffu));
+}
+// Skin one vertex v of a TWO_HAND sample and write it: out = T.R (p0, p1, p2) + T.t, products summed left to right; a left hand's x is
+// negated (optimize_model.py:210-211) and then the shift added (:222-228), two operations -- `kept` (or nullptr) receives the value between
+// them.  dst = the vertex's three floats in verts; a fingertip vertex is also a joint (:201-202) of joints_row = the sample's 42 x 3 row.
+__device__ __forceinline__ void lbs_skin_store(const float (&T)[12], float p0, float p1, float p2, bool left, const float* sShift,
+                                               float* __restrict__ dst, float* __restrict__ joints_row, const int32_t* __restrict__ tip_ids,
+                                               int v, float* __restrict__ kept) {
+    float out[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) out[q] = T[4 * q + 0] * p0 + T[4 * q + 1] * p1 + T[4 * q + 2] * p2 + T[4 * q + 3];
+    if (left) {
+        out[0] = -out[0];
+        if (kept) { kept[0] = out[0]; kept[1] = out[1]; kept[2] = out[2]; }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) out[q] = out[q] + sShift[q];
+    }
+    dst[0] = out[0]; dst[1] = out[1]; dst[2] = out[2];
+#pragma unroll
+    for (int t = 0; t < IHMR_NUM_TIPS; ++t)
+        if (v == tip_ids[t]) {
+            float* jd = joints_row + ((left ? 21 : 0) + NJ + t) * 3;
+            jd[0] = out[0]; jd[1] = out[1]; jd[2] = out[2];
+        }
+}
+// Component k of the left hand's shift: hand_trans + (right wrist - mirrored left wrist), the right wrist of the same sample as
+// J_template[k] + J_shapedirs[k] . beta_right, fma by fma in index order.  sJ_left = the left hand's joints (SK_J of its record).
+__device__ __forceinline__ float lbs_left_shift(const ihmr_mano& m, const float* __restrict__ beta_right, const float* __restrict__ trans_b,
+                                                const float* sJ_left, int k) {
+    float jr = m.J_template[k];
+#pragma unroll
+    for (int l = 0; l < 10; ++l) jr = __builtin_fmaf(m.J_shapedirs[k * 10 + l], beta_right[l], jr);
+    const float jl = k == 0 ? -sJ_left[0] : sJ_left[k];
+    return trans_b[k] + (jr - jl);
+}
+// A sample whose skeletons stand and whose translation (or right-hand shape) moved: the left hand's shift again, into its record in LDS
+// (sk_left) and in global memory (skel_row_left), then its 16 posed joints = (+-G.t) + shift into joints_left_row (the sample's row from
+// joint 21 on).  Every thread of the workgroup must call it (a block-wide barrier inside); tid = its index in the workgroup.
+__device__ __forceinline__ void lbs_retranslate_left(const ihmr_mano& m, const float* __restrict__ shape_right_row,
+                                                     const float* __restrict__ trans_row, float* sk_left, float* __restrict__ skel_row_left,
+                                                     float* __restrict__ joints_left_row, int tid) {
+    if (tid < 3) {
+        const float sh = lbs_left_shift(m, shape_right_row, trans_row, sk_left + SK_J, tid);
+        sk_left[SK_SHIFT + tid] = sh;
+        skel_row_left[SK_SHIFT + tid] = sh;
+    }
+    __syncthreads();
+    if (tid < NJ * 3) {
+        const int j = tid / 3, k = tid % 3;
+        const float val = sk_left[SK_G + 12 * j + 4 * k + 3];
+        joints_left_row[3 * j + k] = (k == 0 ? -val : val) + sk_left[SK_SHIFT + k];
+    }
+}
+// d L / d shift, the block sum of three per-lane partial sums in fixed order: DPP inside each wave, lane 0 of wave i stores to wsum[i]
+// (lbs_wave_sums3); after a barrier of the caller's, the LBS_THREADS / WAVE wave totals of component k in index order (lbs_sum_waves).
+__device__ __forceinline__ void lbs_wave_sums3(float s0, float s1, float s2, float (*wsum)[4], int tid) {
+    s0 = wave_reduce_sum_dpp(s0); s1 = wave_reduce_sum_dpp(s1); s2 = wave_reduce_sum_dpp(s2);
+    if (tid % WAVE == 0) { wsum[tid / WAVE][0] = s0; wsum[tid / WAVE][1] = s1; wsum[tid / WAVE][2] = s2; }
+}
+__device__ __forceinline__ float lbs_sum_waves(const float (*wsum)[4], int k) {
+    float t = 0.f;
+#pragma unroll
+    for (int wv = 0; wv < LBS_THREADS / WAVE; ++wv) t += wsum[wv][k];
+    return t;
+}
+
 // ------------------------------------------------------------------------------------- skeleton
 // 192 threads per hand h (tid = 0..191; every thread of the workgroup must call it: block-wide barriers inside; threads that own
 // no hand call it with active = false and only take part in the barriers).
@@ -116,14 +208,8 @@ __device__ __forceinline__ void lbs_skel_hand(const ihmr_mano& m, const float* _
         sG[e] = c < 3 ? sR[3 * r + c] : sJ[r];
     }
     if (TWO_HAND && left && tid >= 176 && tid < 179) {
-        // right wrist of the same sample: J_r[0] = J_template[0] + J_shapedirs[0] . beta_right
         const int k = tid - 176;
-        const float* br = betas + (h - B) * 10;
-        float jr = m.J_template[k];
-#pragma unroll
-        for (int l = 0; l < 10; ++l) jr = __builtin_fmaf(m.J_shapedirs[k * 10 + l], br[l], jr);
-        const float jl = k == 0 ? -sJ[0] : sJ[k];  // mirrored left wrist
-        sShift[k] = trans[(h - B) * 3 + k] + (jr - jl);
+        sShift[k] = lbs_left_shift(m, betas + (h - B) * 10, trans + (h - B) * 3, sJ, k);
     }
     __syncthreads();
     // kinematic chain, level by level (MANO: depth <= 3); 12 lanes per joint
@@ -360,34 +446,25 @@ __global__ __launch_bounds__(LBS_THREADS) void lbs_skin_kernel(ihmr_mano m, cons
         lbs_v2f T[12];
 #pragma unroll
         for (int e = 0; e < 12; ++e) T[e] = lbs_v2f{0.f, 0.f};
+        auto add_joint = [&](int j, float wgt) {       // the pair's share of joint j (lbs_T_add's sum, two hands per instruction)
+            const lbs_v2f wj = {wgt, wgt};
+            const float4* A4 = reinterpret_cast<const float4*>(&A_s[q][12 * j][0]);   // {A[e] h0, A[e] h1, A[e+1] h0, A[e+1] h1}
+#pragma unroll
+            for (int e2 = 0; e2 < 6; ++e2) {
+                const float4 a = A4[e2];
+                T[2 * e2] = __builtin_elementwise_fma(wj, lbs_v2f{a.x, a.y}, T[2 * e2]);
+                T[2 * e2 + 1] = __builtin_elementwise_fma(wj, lbs_v2f{a.z, a.w}, T[2 * e2 + 1]);
+            }
+        };
         if (m.sparse4) {
             // the same sum without its zero terms (joint order kept; fma(0, a, T) == T): 4 instead of 16 joints, the rows
             // gathered from LDS per lane instead of broadcast
             const float wv[4] = {ws4.x, ws4.y, ws4.z, ws4.w};
 #pragma unroll
-            for (int sI = 0; sI < 4; ++sI) {
-                const int j = (int)((js4 >> (8 * sI)) & 0xffu);
-                const lbs_v2f wj = {wv[sI], wv[sI]};
-                const float4* A4 = reinterpret_cast<const float4*>(&A_s[q][12 * j][0]);
-#pragma unroll
-                for (int e2 = 0; e2 < 6; ++e2) {
-                    const float4 a = A4[e2];
-                    T[2 * e2] = __builtin_elementwise_fma(wj, lbs_v2f{a.x, a.y}, T[2 * e2]);
-                    T[2 * e2 + 1] = __builtin_elementwise_fma(wj, lbs_v2f{a.z, a.w}, T[2 * e2 + 1]);
-                }
-            }
+            for (int sI = 0; sI < 4; ++sI) add_joint((int)((js4 >> (8 * sI)) & 0xffu), wv[sI]);
         } else {
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const lbs_v2f wj = {w[j], w[j]};
-                const float4* A4 = reinterpret_cast<const float4*>(&A_s[q][12 * j][0]);   // {A[e] h0, A[e] h1, A[e+1] h0, A[e+1] h1}
-#pragma unroll
-                for (int e2 = 0; e2 < 6; ++e2) {
-                    const float4 a = A4[e2];
-                    T[2 * e2] = __builtin_elementwise_fma(wj, lbs_v2f{a.x, a.y}, T[2 * e2]);
-                    T[2 * e2 + 1] = __builtin_elementwise_fma(wj, lbs_v2f{a.z, a.w}, T[2 * e2 + 1]);
-                }
-            }
+            for (int j = 0; j < NJ; ++j) add_joint(j, w[j]);
         }
         lbs_v2f o2[3];
 #pragma unroll
@@ -470,21 +547,8 @@ __device__ __forceinline__ void lbs_dvp_vertices(const ihmr_mano& m, const float
         for (int r = 0; r < VR; ++r) {
             const int v = tid + r * LBS_THREADS;
             if (v >= NV) break;
-            const float wv[4] = {wr[r].x, wr[r].y, wr[r].z, wr[r].w};
             float T[12];
-#pragma unroll
-            for (int e = 0; e < 12; ++e) T[e] = 0.f;
-#pragma unroll
-            for (int sI = 0; sI < 4; ++sI) {
-                const float4* A4 = reinterpret_cast<const float4*>(sA + 12 * (int)((jr[r] >> (8 * sI)) & 0xffu));
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const float4 a = A4[q];
-                    T[4 * q] = __builtin_fmaf(wv[sI], a.x, T[4 * q]);
-                    T[4 * q + 1] = __builtin_fmaf(wv[sI], a.y, T[4 * q + 1]);
-                    T[4 * q + 2] = __builtin_fmaf(wv[sI], a.z, T[4 * q + 2]);
-                }
-            }
+            lbs_T_sparse4<3>(T, sA, wr[r], jr[r]);
             put(v, T);
         }
     } else {
@@ -518,16 +582,7 @@ __device__ __forceinline__ void lbs_dvp_vertices(const ihmr_mano& m, const float
 #pragma unroll
             for (int e = 0; e < 12; ++e) T[e] = 0.f;
 #pragma unroll 4
-            for (int j = 0; j < NJ; ++j) {   // 4 joints' rows in flight: unrolled further the LDS reads alone take ~190 VGPRs
-                const float4* A4 = reinterpret_cast<const float4*>(sA + 12 * j);
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const float4 a = A4[q];
-                    T[4 * q] = __builtin_fmaf(w[j], a.x, T[4 * q]);
-                    T[4 * q + 1] = __builtin_fmaf(w[j], a.y, T[4 * q + 1]);
-                    T[4 * q + 2] = __builtin_fmaf(w[j], a.z, T[4 * q + 2]);
-                }
-            }
+            for (int j = 0; j < NJ; ++j) lbs_T_add<3>(T, w[j], sA + 12 * j);   // 4 joints' rows in flight: unrolled further the LDS reads alone take ~190 VGPRs
             put(v, T);
         }
     }
@@ -604,14 +659,10 @@ __device__ __forceinline__ void lbs_bwd1_hand(const ihmr_mano& m, const LbsWork&
 #pragma unroll
         for (int r = 0; r < VR; ++r) { s0 += gl0[r][0]; s1 += gl0[r][1]; s2 += gl0[r][2]; }
         s0 += gjl[0]; s1 += gjl[1]; s2 += gjl[2];
-        // fixed-order block sum: DPP inside each wave, then the 4 wave totals in index order
-        s0 = wave_reduce_sum_dpp(s0); s1 = wave_reduce_sum_dpp(s1); s2 = wave_reduce_sum_dpp(s2);
-        if (tid % WAVE == 0) { bw.wsum[tid / WAVE][0] = s0; bw.wsum[tid / WAVE][1] = s1; bw.wsum[tid / WAVE][2] = s2; }
+        lbs_wave_sums3(s0, s1, s2, bw.wsum, tid);
         __syncthreads();
         if (tid < 3) {
-            float t = 0.f;
-#pragma unroll
-            for (int wv = 0; wv < LBS_THREADS / WAVE; ++wv) t += bw.wsum[wv][tid];
+            const float t = lbs_sum_waves(bw.wsum, tid);
             bw.gsum[tid] = t;
             if (left && need_trans) d_trans[b * 3 + tid] = t;
         }
@@ -675,22 +726,8 @@ __device__ __forceinline__ void lbs_bwd1_hand(const ihmr_mano& m, const LbsWork&
         for (int r = 0; r < VR; ++r) {
             const int v = tid + r * LBS_THREADS;
             if (v >= NV) break;
-            const float wv[4] = {wr[r].x, wr[r].y, wr[r].z, wr[r].w};
             float T[12];
-#pragma unroll
-            for (int e = 0; e < 12; ++e) T[e] = 0.f;
-#pragma unroll
-            for (int sI = 0; sI < 4; ++sI) {
-                const float4* A4 = reinterpret_cast<const float4*>(sA + 12 * (int)((jr[r] >> (8 * sI)) & 0xffu));
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const float4 a = A4[q];
-                    T[4 * q] = __builtin_fmaf(wv[sI], a.x, T[4 * q]);
-                    T[4 * q + 1] = __builtin_fmaf(wv[sI], a.y, T[4 * q + 1]);
-                    T[4 * q + 2] = __builtin_fmaf(wv[sI], a.z, T[4 * q + 2]);
-                    T[4 * q + 3] = __builtin_fmaf(wv[sI], a.w, T[4 * q + 3]);
-                }
-            }
+            lbs_T_sparse4<4>(T, sA, wr[r], jr[r]);
             const float p0 = bw.vp[3 * v], p1 = bw.vp[3 * v + 1], p2 = bw.vp[3 * v + 2];
             const float g[3] = {bw.g[3 * v], bw.g[3 * v + 1], bw.g[3 * v + 2]};
 #pragma unroll

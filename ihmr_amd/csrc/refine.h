@@ -358,6 +358,14 @@ __device__ __forceinline__ void opt_param_apply(const ihmr_opt_io& io, const Opt
 __device__ __forceinline__ void opt_snapshot_losses(const ihmr_opt_io& io, int B, const ParamStep& st, int b, int e) {
     if (st.snap_idx >= 0 && e < 3) io.snap_loss[((size_t)st.snap_idx * 3 + e) * B + b] = io.loss_batch[e * B + b];
 }
+// What closes an iteration inside the workgroup of sample b (thread tid): sample 0's threads [zero_from_tid, zero_from_tid + SDF_NZERO)
+// zero the inside-voxel counters that the next iteration's collision kernels append to; threads e < 122 take the loss snapshot and
+// step their parameter slot.  The caller's barrier publishes the new parameters.
+__device__ __forceinline__ void opt_step_sample(const ihmr_opt_io& io, const OptWork& wk, int B, const ParamStep& st, int* inside_count,
+                                                int zero_from_tid, int b, int tid) {
+    if (b == 0 && tid >= zero_from_tid && tid < zero_from_tid + SDF_NZERO) sdf_zero_counter(inside_count, tid - zero_from_tid);
+    if (st.mask && tid < OPT_NPARAM) { opt_snapshot_losses(io, B, st, b, tid); opt_param_apply(io, wk, B, st, b, tid); }
+}
 
 // stand-alone step (the last iteration of a stage): grid = B, block = 128, thread e < 122.  The shape slots read
 // both hands' values of a sample while updating them: they sit in one wave (slots 102..121), reads before writes.
@@ -375,10 +383,8 @@ __global__ __launch_bounds__(384) void opt_adam_skel_kernel(ihmr_mano m, ihmr_op
     TL_SCOPE(7);
     __shared__ float sk[2][SK_STRIDE];
     const int b = blockIdx.x, tid = threadIdx.x;
-    // the collision kernels of this iteration append to the inside-voxel counter: start it at zero
-    if (b == 0 && tid >= 192 && tid < 192 + SDF_NZERO) sdf_zero_counter(inside_count, tid - 192);
     if (st.reset_state && tid < OPT_NPARAM) { io.adam_m[b * OPT_NPARAM + tid] = 0.f; io.adam_v[b * OPT_NPARAM + tid] = 0.f; }
-    if (st.mask && tid < OPT_NPARAM) { opt_snapshot_losses(io, B, st, b, tid); opt_param_apply(io, wk, B, st, b, tid); }
+    opt_step_sample(io, wk, B, st, inside_count, 192, b, tid);
     __syncthreads();   // the updated parameters are read back below by other threads of this workgroup
     const int hl = tid / 192;
     lbs_skel_hand<true>(m, io.orient, io.pose, io.shape, io.trans, B, wk.lbs.skel, wk.joints_raw, sk[hl], hl * B + b, tid % 192);
@@ -392,7 +398,7 @@ __global__ __launch_bounds__(384) void opt_adam_skel_kernel(ihmr_mano m, ihmr_op
 // changes -- the phases are the same device functions, the results the same bits.  grid = B, block = 512, 2 workgroups per CU
 // (~56 KB static + 2 x nseg x 48 B dynamic LDS).
 // SKIN (with STEP, stages that keep v_posed -- neither finger pose nor shape moves): a fourth phase skins the stored v_posed of both
-// hands with the skeletons just computed (= lbs_skin_kernel<true, REUSE>, the same operations in the same order: the same bits), so
+// hands with the skeletons just computed (= lbs_skin_kernel<true, REUSE> in scalar form: lbs_T_sparse4 / lbs_T_add, lbs_skin_store), so
 // the next iteration starts at the collision kernels: 3 launches per iteration.
 // Each stage's tail does only what the stage can move: a stage that moves ONLY the translation (need_mask == 8) runs opt_tail_kernel_trans
 // below instead of the <true, true> form (no second skinning of hands whose pre-shift vertices cannot change), and in the STEP phase a hand
@@ -439,6 +445,26 @@ __device__ __forceinline__ const TailArgs& tail_args() {
     asm volatile("" : "+s"(p));
     return *(const TailArgs*)p;
 }
+// Phase 1 of both tails: collision sampling (waves 0-6) + joint / translation / finger losses (wave 7) of sample b.  Their gradients --
+// d L / d vertices, d L / d joints -- go to the two hands' LDS records rec[0], rec[1] (REC: LbsBwdShared or TransTailHand: `g` and `gj`, raw
+// hand frame), not through global memory (the same values).  One workgroup barrier inside, at the same place for both kinds of wave: the
+// block sum -- every thread of the workgroup must call it.  The arguments are the caller's by-value copies of the TailArgs fields.
+template <class REC>
+__device__ __forceinline__ void tail_sample_and_losses(const ihmr_opt_io& io, const OptWork& wk, int B, const ihmr_opt_weights& w,
+                                                       const SdfWorkspace& ws, const VertLayout& vl, int need_cam, LossShared& sh, float* red16,
+                                                       REC* rec, int b, int tid) {
+    const float mask = (io.hand_type_array[b * 2] + io.hand_type_array[b * 2 + 1]) > 1.5f ? 1.f : 0.f;
+    const float gs = w.collision * mask / (ws.loss_div * (float)(io.norm_batch > 0 ? io.norm_batch : B));
+    if (tid >= OPT_SAMPLE_WORKERS) {
+        opt_loss_wave(io, wk, B, w, sh, b, tid - OPT_SAMPLE_WORKERS, need_cam, rec);
+        if (tid == OPT_SAMPLE_WORKERS) red16[OPT_SAMPLE_WORKERS / WAVE] = 0.f;       // (its share of the block sum)
+        __syncthreads();
+    } else {
+        // (inside the loop nobody reads the per-vertex depths: the 12 KB per sample and iteration are not written -- the forward that
+        // closes optimize(), opt_sample_loss_kernel, writes the ones that are exported)
+        sdf_sample_cells(vl, ws, io.loss_batch + 2 * B, B, io.hand_type_array, red16, b, OPT_SAMPLE_WORKERS, SdfEmitTail{gs, rec[0].g, rec[1].g});
+    }
+}
 template <bool STEP, bool SKIN = false>
 __global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel(TailArgs) {
     TL_SCOPE(3 + (STEP ? 1 : 0) + (SKIN ? 1 : 0));
@@ -467,20 +493,8 @@ __global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel(TailArg
     } else if (SKIN) {       // translation stage: the skeleton records stay valid for the next iteration's vertices (phase 3 / 4)
         lds_dma_dwords(wk.lbs.skel + (size_t)(hl * B + b) * SK_STRIDE, bw[hl].sk, SK_STRIDE, tid % LBS_THREADS, LBS_THREADS);
     }
-    // ---- phase 1: collision sampling (waves 0-6) + joint / translation / finger losses (wave 7).  Their gradients -- d L / d vertices,
-    //      d L / d joints -- are handed to phase 2 through its LDS records, not through global memory (the same values).  One workgroup
-    //      barrier inside, at the same place for both kinds of wave: the block sum
-    const float mask = (io.hand_type_array[b * 2] + io.hand_type_array[b * 2 + 1]) > 1.5f ? 1.f : 0.f;
-    const float gs = w.collision * mask / (ws.loss_div * (float)(io.norm_batch > 0 ? io.norm_batch : B));
-    if (tid >= OPT_SAMPLE_WORKERS) {
-        opt_loss_wave(io, wk, B, w, sh, b, tid - OPT_SAMPLE_WORKERS, a.need_cam, bw);
-        if (tid == OPT_SAMPLE_WORKERS) red16[OPT_SAMPLE_WORKERS / WAVE] = 0.f;       // (its share of the block sum)
-        __syncthreads();
-    } else {
-        // (inside the loop nobody reads the per-vertex depths: the 12 KB per sample and iteration are not written -- the forward that
-        // closes optimize(), opt_sample_loss_kernel, writes the ones that are exported)
-        sdf_sample_cells(vl, ws, io.loss_batch + 2 * B, B, io.hand_type_array, red16, b, OPT_SAMPLE_WORKERS, SdfEmitTail{gs, bw[0].g, bw[1].g});
-    }
+    // ---- phase 1: collision sampling + losses; their gradients are handed to phase 2 through its LDS records
+    tail_sample_and_losses(io, wk, B, w, ws, vl, a.need_cam, sh, red16, bw, b, tid);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (this wave's DMA writes to LDS have landed; the barrier publishes them)
     __syncthreads();         // the gradients of this sample and the DMA'd records: written above by this workgroup, read below by it
@@ -499,8 +513,7 @@ __global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel(TailArg
     {
     const TailArgs& a = tail_args();
     const ihmr_opt_io io = a.io; const OptWork wk = a.wk; const ParamStep st = a.st;
-    if (b == 0 && tid >= 384 && tid < 384 + SDF_NZERO) sdf_zero_counter(a.inside_count, tid - 384);   // the next iteration's collision kernels start from zero
-    if (st.mask && tid < OPT_NPARAM) { opt_snapshot_losses(io, a.B, st, b, tid); opt_param_apply(io, wk, a.B, st, b, tid); }
+    opt_step_sample(io, wk, a.B, st, a.inside_count, 384, b, tid);
     }
     __syncthreads();         // the updated parameters are read back below by other threads of this workgroup
     TAIL_TK(2);
@@ -526,26 +539,10 @@ __global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel(TailArg
     }
     if (SKIN && (need_mask & 7) == 0) {
         // Translation stage: neither skeleton changes -- the records DMA'd into LDS in phase 0 ARE the next iteration's -- except the left hand's
-        // shift (= hand_trans + right wrist - mirrored left wrist) and with it the left hand's posed joints.  The three shift components are
-        // recomputed with lbs_skel_hand's own expression (the same bits) instead of both skeletons (Rodrigues, joint regression, chain by level:
-        // 3.8 us of the 512-sample launch).
-        if (tid < 3) {
-            const float* br = io.shape + (size_t)b * 10;                 // right wrist: J_template[0] + J_shapedirs[0] . beta_right
-            float jr = m.J_template[tid];
-#pragma unroll
-            for (int l = 0; l < 10; ++l) jr = __builtin_fmaf(m.J_shapedirs[tid * 10 + l], br[l], jr);
-            const float* sJl = bw[1].sk + SK_J;
-            const float jl = tid == 0 ? -sJl[0] : sJl[tid];              // mirrored left wrist
-            const float sh = io.trans[b * 3 + tid] + (jr - jl);
-            bw[1].sk[SK_SHIFT + tid] = sh;
-            wk.lbs.skel[((size_t)B + b) * SK_STRIDE + SK_SHIFT + tid] = sh;
-        }
-        __syncthreads();
-        if (tid < NJ * 3) {
-            const int j = tid / 3, k = tid % 3;
-            const float val = bw[1].sk[SK_G + 12 * j + 4 * k + 3];
-            wk.joints_raw[((size_t)b * 42 + 21 + j) * 3 + k] = (k == 0 ? -val : val) + bw[1].sk[SK_SHIFT + k];
-        }
+        // shift and with it the left hand's posed joints: lbs_retranslate_left instead of both skeletons (Rodrigues, joint regression, chain
+        // by level: 3.8 us of the 512-sample launch).
+        lbs_retranslate_left(m, io.shape + (size_t)b * 10, io.trans + b * 3, bw[1].sk, wk.lbs.skel + ((size_t)B + b) * SK_STRIDE,
+                             wk.joints_raw + ((size_t)b * 42 + 21) * 3, tid);
     } else {
         const int hs = tid / 192;
         // (keep_rot: a hand none of whose axis-angles the stage refines keeps sR / the pose feature of the record phase 0 brought in)
@@ -563,45 +560,15 @@ __global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel(TailArg
         const int v = lt + r * LBS_THREADS;
         if (v >= NV) break;
         float T[12];
-#pragma unroll
-        for (int e = 0; e < 12; ++e) T[e] = 0.f;
         if (m.sparse4) {
-            const float wv[4] = {wr[r].x, wr[r].y, wr[r].z, wr[r].w};
-#pragma unroll
-            for (int sI = 0; sI < 4; ++sI) {
-                const float4* A4 = reinterpret_cast<const float4*>(sA + 12 * (int)((jr[r] >> (8 * sI)) & 0xffu));
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const float4 a = A4[q];
-                    T[4 * q] = __builtin_fmaf(wv[sI], a.x, T[4 * q]);
-                    T[4 * q + 1] = __builtin_fmaf(wv[sI], a.y, T[4 * q + 1]);
-                    T[4 * q + 2] = __builtin_fmaf(wv[sI], a.z, T[4 * q + 2]);
-                    T[4 * q + 3] = __builtin_fmaf(wv[sI], a.w, T[4 * q + 3]);
-                }
-            }
+            lbs_T_sparse4<4>(T, sA, wr[r], jr[r]);
         } else {
-            for (int j = 0; j < NJ; ++j) {
-                const float wj = m.weights[v * NJ + j];
 #pragma unroll
-                for (int e = 0; e < 12; ++e) T[e] = __builtin_fmaf(wj, sA[12 * j + e], T[e]);
-            }
+            for (int e = 0; e < 12; ++e) T[e] = 0.f;
+            for (int j = 0; j < NJ; ++j) lbs_T_add<4>(T, m.weights[v * NJ + j], sA + 12 * j);
         }
-        float out[3];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) out[q] = T[4 * q + 0] * vp[r][0] + T[4 * q + 1] * vp[r][1] + T[4 * q + 2] * vp[r][2] + T[4 * q + 3];
-        if (hl == 1) {  // optimize_model.py:210-211, 222-228
-            out[0] = -out[0] + sShift[0];
-            out[1] = out[1] + sShift[1];
-            out[2] = out[2] + sShift[2];
-        }
-        float* dst = io.verts + ((size_t)hv * NV + v) * 3;
-        dst[0] = out[0]; dst[1] = out[1]; dst[2] = out[2];
-#pragma unroll
-        for (int t = 0; t < IHMR_NUM_TIPS; ++t)
-            if (v == m.tip_ids[t]) {  // fingertip joints are vertices (:201-202)
-                float* jd = wk.joints_raw + ((size_t)b * 42 + (hl ? 21 : 0) + NJ + t) * 3;
-                jd[0] = out[0]; jd[1] = out[1]; jd[2] = out[2];
-            }
+        lbs_skin_store(T, vp[r][0], vp[r][1], vp[r][2], hl == 1, sShift, io.verts + ((size_t)hv * NV + v) * 3, wk.joints_raw + (size_t)b * 42 * 3,
+                       m.tip_ids, v, nullptr);
     }
     TAIL_TK(4);
 }
@@ -612,11 +579,11 @@ __global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel(TailArg
 //   * the right hand does not move at all -- its vertices, fingertip joints and skeleton record stay what the stage's first iteration made;
 //   * the left hand only translates: its skinned vertex before the shift, T . v_posed + T3 with x negated, is the same bits in every
 //     iteration; what changes is the one addition of the shift per coordinate.
-// So the stage's first STEP launch (TailArgs::fill_kept) skins the left hand exactly as the generic phase 4 does and stores the value
-// BEFORE the shift is added (OptWork::kept_left), and every launch writes verts = kept + shift: the generic form's last operation on the
-// same operands, hence the same bits.  Phases 1-3 are the generic form's device functions and expressions; of the LBS backward only the
-// left-hand gradient sum (= d L / d shift, lbs_bwd1_hand's first block: lane partials in r order, DPP wave sums, the four wave totals in
-// index order) is left.  No v_posed, no right-hand record, no dynamic LDS: ~27 KB of static LDS, and the registers of the sampler.
+// So the stage's first STEP launch (TailArgs::fill_kept) skins the left hand with the generic phase 4's helpers (lbs_T_sparse4 / lbs_T_add,
+// lbs_skin_store) and stores the value BEFORE the shift is added (OptWork::kept_left), and every launch writes verts = kept + shift: the
+// generic form's last operation on the same operands, hence the same bits.  Phases 1-3 are the generic form's device functions; of the LBS
+// backward only the left-hand gradient sum (= d L / d shift, lbs_bwd1_hand's first block: lane partials in r order, then lbs_wave_sums3 /
+// lbs_sum_waves) is left.  No v_posed, no right-hand record, no dynamic LDS: ~27 KB of static LDS, and the registers of the sampler.
 struct TransTailHand { float g[NV3]; float gj[21][3]; };      // what phase 1 writes per hand (raw hand frame)
 __global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel_trans(TailArgs) {
     TL_SCOPE(5);
@@ -633,16 +600,8 @@ __global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel_trans(T
     const ihmr_opt_io io = a.io; const OptWork wk = a.wk; const ihmr_opt_weights w = a.w; const SdfWorkspace ws = a.ws;
     const VertLayout vl = a.vl;
     lds_dma_dwords(wk.lbs.skel + ((size_t)B + b) * SK_STRIDE, skl, SK_STRIDE, tid, SDF_SAMPLE_THREADS);
-    // ---- phase 1: collision sampling + losses, as opt_tail_kernel
-    const float mask = (io.hand_type_array[b * 2] + io.hand_type_array[b * 2 + 1]) > 1.5f ? 1.f : 0.f;
-    const float gs = w.collision * mask / (ws.loss_div * (float)(io.norm_batch > 0 ? io.norm_batch : B));
-    if (tid >= OPT_SAMPLE_WORKERS) {
-        opt_loss_wave(io, wk, B, w, sh, b, tid - OPT_SAMPLE_WORKERS, a.need_cam, th);
-        if (tid == OPT_SAMPLE_WORKERS) red16[OPT_SAMPLE_WORKERS / WAVE] = 0.f;
-        __syncthreads();
-    } else {
-        sdf_sample_cells(vl, ws, io.loss_batch + 2 * B, B, io.hand_type_array, red16, b, OPT_SAMPLE_WORKERS, SdfEmitTail{gs, th[0].g, th[1].g});
-    }
+    // ---- phase 1: collision sampling + losses
+    tail_sample_and_losses(io, wk, B, w, ws, vl, a.need_cam, sh, red16, th, b, tid);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -660,16 +619,10 @@ __global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel_trans(T
         float gjl[3] = {0.f, 0.f, 0.f};
         if (tid < 21) { gjl[0] = -th[1].gj[tid][0]; gjl[1] = th[1].gj[tid][1]; gjl[2] = th[1].gj[tid][2]; }
         s0 += gjl[0]; s1 += gjl[1]; s2 += gjl[2];
-        s0 = wave_reduce_sum_dpp(s0); s1 = wave_reduce_sum_dpp(s1); s2 = wave_reduce_sum_dpp(s2);
-        if (tid % WAVE == 0) { wsum[tid / WAVE][0] = s0; wsum[tid / WAVE][1] = s1; wsum[tid / WAVE][2] = s2; }
+        lbs_wave_sums3(s0, s1, s2, wsum, tid);
     }
     __syncthreads();
-    if (tid < 3) {
-        float t = 0.f;
-#pragma unroll
-        for (int wv = 0; wv < LBS_THREADS / WAVE; ++wv) t += wsum[wv][tid];
-        tail_args().wk.g_trans[b * 3 + tid] = t;
-    }
+    if (tid < 3) tail_args().wk.g_trans[b * 3 + tid] = lbs_sum_waves(wsum, tid);
     __syncthreads();         // the translation gradient of this sample is in place
     // ---- phase 3: the optimizer step of this iteration; the kept vertices of phase 4 are requested ahead of it
     constexpr int ER = (NV3 + SDF_SAMPLE_THREADS - 1) / SDF_SAMPLE_THREADS;
@@ -684,31 +637,15 @@ __global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel_trans(T
         for (int r = 0; r < ER; ++r) kept[r] = wk.kept_left[(size_t)b * NV3 + min(tid + r * SDF_SAMPLE_THREADS, NV3 - 1)];
         if (tid < IHMR_NUM_TIPS * 3) kept_tip = wk.kept_left[(size_t)b * NV3 + 3 * a.m.tip_ids[tid / 3] + tid % 3];
     }
-    if (b == 0 && tid >= 384 && tid < 384 + SDF_NZERO) sdf_zero_counter(a.inside_count, tid - 384);
-    if (st.mask && tid < OPT_NPARAM) { opt_snapshot_losses(io, a.B, st, b, tid); opt_param_apply(io, wk, a.B, st, b, tid); }
+    opt_step_sample(io, wk, a.B, st, a.inside_count, 384, b, tid);
     }
     __syncthreads();         // the updated parameters are read back below by other threads of this workgroup
     const TailArgs& a = tail_args();
     const int B = a.B;
     const ihmr_mano m = a.m; const ihmr_opt_io io = a.io; const OptWork wk = a.wk;
-    // the left hand's shift (= hand_trans + right wrist - mirrored left wrist) with lbs_skel_hand's own expression, and its posed joints
-    if (tid < 3) {
-        const float* br = io.shape + (size_t)b * 10;                 // right wrist: J_template[0] + J_shapedirs[0] . beta_right
-        float jr = m.J_template[tid];
-#pragma unroll
-        for (int l = 0; l < 10; ++l) jr = __builtin_fmaf(m.J_shapedirs[tid * 10 + l], br[l], jr);
-        const float* sJl = skl + SK_J;
-        const float jl = tid == 0 ? -sJl[0] : sJl[tid];              // mirrored left wrist
-        const float sh = io.trans[b * 3 + tid] + (jr - jl);
-        skl[SK_SHIFT + tid] = sh;
-        wk.lbs.skel[((size_t)B + b) * SK_STRIDE + SK_SHIFT + tid] = sh;
-    }
-    __syncthreads();
-    if (tid < NJ * 3) {
-        const int j = tid / 3, k = tid % 3;
-        const float val = skl[SK_G + 12 * j + 4 * k + 3];
-        wk.joints_raw[((size_t)b * 42 + 21 + j) * 3 + k] = (k == 0 ? -val : val) + skl[SK_SHIFT + k];
-    }
+    // the left hand's shift and its posed joints
+    lbs_retranslate_left(m, io.shape + (size_t)b * 10, io.trans + b * 3, skl, wk.lbs.skel + ((size_t)B + b) * SK_STRIDE,
+                         wk.joints_raw + ((size_t)b * 42 + 21) * 3, tid);
     // ---- phase 4: the next iteration's left-hand vertices = kept + shift (the right hand's stay)
     const float* sShift = skl + SK_SHIFT;
     float* dstv = io.verts + ((size_t)B + b) * NV3;
@@ -720,47 +657,16 @@ __global__ __launch_bounds__(SDF_SAMPLE_THREADS, 4) void opt_tail_kernel_trans(T
             const float* s0 = wk.lbs.v_posed + ((size_t)(B + b) * NV + v) * 3;
             const float vp[3] = {s0[0], s0[1], s0[2]};
             float T[12];
-#pragma unroll
-            for (int e = 0; e < 12; ++e) T[e] = 0.f;
             if (m.sparse4) {
-                const float4 wr = m.w4_w[v];
-                const uint32_t jr = m.w4_j[v];
-                const float wv[4] = {wr.x, wr.y, wr.z, wr.w};
-#pragma unroll
-                for (int sI = 0; sI < 4; ++sI) {
-                    const float4* A4 = reinterpret_cast<const float4*>(sA + 12 * (int)((jr >> (8 * sI)) & 0xffu));
-#pragma unroll
-                    for (int q = 0; q < 3; ++q) {
-                        const float4 a4 = A4[q];
-                        T[4 * q] = __builtin_fmaf(wv[sI], a4.x, T[4 * q]);
-                        T[4 * q + 1] = __builtin_fmaf(wv[sI], a4.y, T[4 * q + 1]);
-                        T[4 * q + 2] = __builtin_fmaf(wv[sI], a4.z, T[4 * q + 2]);
-                        T[4 * q + 3] = __builtin_fmaf(wv[sI], a4.w, T[4 * q + 3]);
-                    }
-                }
+                lbs_T_sparse4<4>(T, sA, m.w4_w[v], m.w4_j[v]);
             } else {
+#pragma unroll
+                for (int e = 0; e < 12; ++e) T[e] = 0.f;
 #pragma unroll 1
-                for (int j = 0; j < NJ; ++j) {
-                    const float wj = m.weights[v * NJ + j];
-#pragma unroll
-                    for (int e = 0; e < 12; ++e) T[e] = __builtin_fmaf(wj, sA[12 * j + e], T[e]);
-                }
+                for (int j = 0; j < NJ; ++j) lbs_T_add<4>(T, m.weights[v * NJ + j], sA + 12 * j);
             }
-            float out[3];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) out[q] = T[4 * q + 0] * vp[0] + T[4 * q + 1] * vp[1] + T[4 * q + 2] * vp[2] + T[4 * q + 3];
-            out[0] = -out[0];
-            float* kd = wk.kept_left + (size_t)b * NV3 + 3 * v;
-            kd[0] = out[0]; kd[1] = out[1]; kd[2] = out[2];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) out[q] = out[q] + sShift[q];
-            dstv[3 * v] = out[0]; dstv[3 * v + 1] = out[1]; dstv[3 * v + 2] = out[2];
-#pragma unroll
-            for (int t = 0; t < IHMR_NUM_TIPS; ++t)
-                if (v == m.tip_ids[t]) {  // fingertip joints are vertices
-                    float* jd = wk.joints_raw + ((size_t)b * 42 + 21 + NJ + t) * 3;
-                    jd[0] = out[0]; jd[1] = out[1]; jd[2] = out[2];
-                }
+            lbs_skin_store(T, vp[0], vp[1], vp[2], true, sShift, dstv + 3 * v, wk.joints_raw + (size_t)b * 42 * 3, m.tip_ids, v,
+                           wk.kept_left + (size_t)b * NV3 + 3 * v);
         }
         return;
     }

@@ -43,6 +43,8 @@ def _stages(epoch, which):
     trans, orient, pose, shape = make_opt_strategy(epoch)
     if which == "trans":
         return [trans]
+    if which == "orient":
+        return [orient]
     if which == "trans-cam":
         return [dict(trans, update_params=["pred_hand_trans", "pred_cam_params"])]
     if which == "shape":
@@ -53,15 +55,17 @@ def _stages(epoch, which):
     return [trans, orient, pose, shape]
 
 
-def _run(batch, B, epoch, freq, which, generic=False, full=True, **extra):
+def _run(batch, B, epoch, freq, which, generic=False, full=True, prepare=None, **extra):
     """One fresh instance (its stage graphs are captured under the switch), two passes (capture, replay).  full: optimize() as the
-    driver runs it (the closing forward included); otherwise the stages alone."""
+    driver runs it (the closing forward included); otherwise the stages alone.  prepare: called with the instance before its first input."""
     from ihmr_amd import hip
     from ihmr_amd.optimize_model import OptimizeModel
     prev = hip.lib().ihmr_debug_force_generic_tail(1 if generic else 0)
     try:
         m = OptimizeModel(_make_opt(B, epoch, freq, **extra))
         m.strategy = _stages(epoch, which)
+        if prepare is not None:
+            prepare(m)
         for rep in range(2):
             m.set_input(batch); m.init_optimize(); m.optimize()
             torch.cuda.synchronize()
@@ -147,3 +151,39 @@ def test_left_shape_only_stage(mano_arrays):
     batch = _batch(mano_arrays, "default", 3)
     out = _check(batch, 3, 2, 1, "left-shape")
     assert np.abs(out["state/adam_m"][:, 112:]).max() > 0 and np.abs(out["state/adam_m"][:, 102:112]).max() == 0
+
+
+TAIL_STATIC_LDS = 55840     # opt_tail_kernel's static LDS (tests/test_tail_build_cpu.py reads it from the build)
+LDS_PER_WORKGROUP = 163840  # a workgroup's limit on gfx950: the fused tail is taken only when static + dynamic LDS fit it
+
+
+def _dense_weights(arrays):
+    """The lbs_weights of test_gpu_parity._dense_weight_asset, checked on the host: some vertex has more than four non-zero weights (the
+    kernels take their 16-joint loops) and the fused tail still fits -- 2 x 48 B of dynamic LDS per single-joint segment of <= 13 entries
+    (csrc/mano_lbs.h: LBS_SEG); otherwise the fused runs and the separate launches would be the same launches."""
+    from test_gpu_parity import _dense_weight_asset
+    w = _dense_weight_asset(arrays)["lbs_weights"]
+    assert int((w != 0).sum(axis=1).max()) > 4
+    nseg = int(sum(-(-int(n) // 13) for n in (w != 0).sum(axis=0)))
+    assert TAIL_STATIC_LDS + 2 * 48 * nseg <= LDS_PER_WORKGROUP, nseg
+    return w
+
+
+@pytest.mark.parametrize("which", ["trans", "orient"])
+def test_dense_weights_reach_the_tails(mano_arrays, which):
+    """The 16-joint blend of the tails' skinning phases, which MANO's own four weights per vertex never reach: three iterations of a
+    translation stage (`opt_tail_kernel_trans`: the filling launch, then kept + shift) and of an orientation stage (`opt_tail_kernel<true,
+    true>` phase 4) on an asset with up to seven weights per vertex, against the generic tail forms and against the separate launches
+    (`lbs_skin_kernel` REUSE), bit for bit."""
+    dense = {True: _dense_weights(mano_arrays[0]), False: _dense_weights(mano_arrays[1])}       # (asserted before anything is launched)
+
+    def use_dense_weights(m):
+        """Both MANO modules of a fresh instance: their device constants are made on first use, from these arrays."""
+        for module in m.mano_models.values():
+            module._arrays["lbs_weights"] = dense[module.is_rhand]
+            module._dev_handle = None
+
+    batch = _batch(mano_arrays, "default", 3)
+    out = _check(batch, 3, 2, 1, which, prepare=use_dense_weights)
+    lo = 3 if which == "trans" else 6
+    assert np.abs(out["state/adam_m"][:, lo:lo + 3]).max() > 0, "the stage computed no gradient"
