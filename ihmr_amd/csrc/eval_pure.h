@@ -121,3 +121,49 @@ EVP_PURE double evp_aligned_error(const evp_transform& T, const double* p, const
     const double dz = (T.scale * ((T.R[2][0] * p[0] + T.R[2][1] * p[1]) + T.R[2][2] * p[2]) + T.t[2]) - g[2];
     return sqrt((dx * dx + dy * dy) + dz * dz);
 }
+
+// scale * R * p + t, the operations of evp_aligned_error in the same order
+EVP_PURE void evp_aligned_point(const evp_transform& T, const double* p, double* out) {
+    out[0] = T.scale * ((T.R[0][0] * p[0] + T.R[0][1] * p[1]) + T.R[0][2] * p[2]) + T.t[0];
+    out[1] = T.scale * ((T.R[1][0] * p[0] + T.R[1][1] * p[1]) + T.R[1][2] * p[2]) + T.t[1];
+    out[2] = T.scale * ((T.R[2][0] * p[0] + T.R[2][1] * p[1]) + T.R[2][2] * p[2]) + T.t[2];
+}
+
+// ------------------------------------------------------------------------------------------ curve metrics: PCK counts and F-scores
+// The THRESHOLD INDEX of a value v in an ascending table t[0..T): the number of thresholds that v exceeds.  Thresholds ascend, so
+// the exceeded ones are t[0..idx) and the comparison holds for every k >= idx: a histogram over idx, summed from the left, is the
+// count per threshold.  Two forms:
+//   evp_threshold_index         idx = #{k : !(v <= t[k])}     v <= t[k] for k >= idx     (PCK: the comparison is non-strict)
+//   evp_threshold_index_strict  idx = #{k : !(v <  t[k])}     v <  t[k] for k >= idx     (F-score, collision AUC: strict)
+// A NaN satisfies no comparison and gets idx = T.  Binary search over memory (at most 9 probes for T <= 256): `t` is a pointer into
+// LDS or global memory on the device, never a register array that a run-time index would push into scratch memory.
+EVP_PURE int evp_threshold_index(double v, const double* t, int T) {
+    int lo = 0, hi = T;                       // t[0..lo) exceeded, t[hi..T) not
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (v <= t[mid]) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+EVP_PURE int evp_threshold_index_strict(double v, const double* t, int T) {
+    int lo = 0, hi = T;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (v < t[mid]) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// |a - b|^2 in the one bracketed order that host and device share: (dx * dx + dy * dy) + dz * dz.  The nearest-neighbour search
+// takes the minimum of these (exact, so the order of the search cannot change a bit) and the root once
+EVP_PURE double evp_sq_dist(double ax, double ay, double az, double bx, double by, double bz) {
+    const double dx = ax - bx, dy = ay - by, dz = az - bz;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// F = 2 P R / (P + R) of one hand from its two counts, P = n_pg / n and R = n_gp / n; 0 when P + R = 0
+EVP_PURE double evp_fscore(double n_pg, double n_gp, double n) {
+    const double P = n_pg / n, R = n_gp / n;
+    return P + R > 0.0 ? 2.0 * P * R / (P + R) : 0.0;
+}

@@ -151,6 +151,38 @@ __device__ __forceinline__ double wave_reduce_sum_f64(double v) {
     return v;
 }
 
+// One joint set of one sample, one wave: `in_set` marks the lanes whose joint belongs to the set, a member is one of them with w > 0.
+// Returns the lane's aligned error / sc (0 for a non-member and for a set left out), n = the number of members, kept = the set counts.
+__device__ __forceinline__ double pa_joint_set_error(bool in_set, double w, const double (&p)[3], const double (&g)[3], double sc,
+                                                     double& n, bool& kept) {
+    const bool member = in_set && w > 0.0;
+    const double wsum = wave_reduce_sum_f64(in_set ? w : 0.0);
+    n = wave_reduce_sum_f64(member ? 1.0 : 0.0);
+    double err = 0.0;
+    kept = false;
+    if (wsum >= EVP_MIN_WEIGHT_SUM && n > 0.0) {          // uniform over the wave
+        double m1[3], m2[3], x1[3], x2[3], M[3][3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            m1[k] = wave_reduce_sum_f64(member ? p[k] : 0.0) / n;
+            m2[k] = wave_reduce_sum_f64(member ? g[k] : 0.0) / n;
+            x1[k] = member ? p[k] - m1[k] : 0.0;
+            x2[k] = member ? g[k] - m2[k] : 0.0;
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) M[a][c] = wave_reduce_sum_f64(x1[a] * x2[c]);
+        const double var1 = wave_reduce_sum_f64((x1[0] * x1[0] + x1[1] * x1[1]) + x1[2] * x1[2]);
+        if (var1 > 0.0) {
+            kept = true;
+            const evp_transform T = procrustes_from_moments(n, m1, m2, M, var1);
+            if (member) err = evp_aligned_error(T, p, g) / sc;
+        }
+    }
+    return err;
+}
+
 // grid = B, block = 64: lane j < 42 owns joint j.  Three sets per sample: 0 = all valid joints (the reference's call), 1 = the valid
 // joints of the right hand (0..20), 2 = those of the left hand (21..41).  out (B,3,2) doubles [sum of errors, count];
 // point_err (B,3,42) doubles or NULL: the aligned error of a set's member, 0 for every other joint and for a set left out.
@@ -169,32 +201,9 @@ __global__ __launch_bounds__(64) void eval_pa_joints_kernel(const float* __restr
 #pragma nounroll
     for (int s = 0; s < 3; ++s) {
         const int lo = s == 2 ? 21 : 0, hi = s == 1 ? 21 : 42;
-        const bool in_set = act && j >= lo && j < hi;
-        const bool member = in_set && w > 0.0;
-        const double wsum = wave_reduce_sum_f64(in_set ? w : 0.0);
-        const double n = wave_reduce_sum_f64(member ? 1.0 : 0.0);
-        double err = 0.0;
-        bool kept = false;
-        if (wsum >= EVP_MIN_WEIGHT_SUM && n > 0.0) {          // uniform over the wave
-            double m1[3], m2[3], x1[3], x2[3], M[3][3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                m1[k] = wave_reduce_sum_f64(member ? p[k] : 0.0) / n;
-                m2[k] = wave_reduce_sum_f64(member ? g[k] : 0.0) / n;
-                x1[k] = member ? p[k] - m1[k] : 0.0;
-                x2[k] = member ? g[k] - m2[k] : 0.0;
-            }
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) M[a][c] = wave_reduce_sum_f64(x1[a] * x2[c]);
-            const double var1 = wave_reduce_sum_f64((x1[0] * x1[0] + x1[1] * x1[1]) + x1[2] * x1[2]);
-            if (var1 > 0.0) {
-                kept = true;
-                const evp_transform T = procrustes_from_moments(n, m1, m2, M, var1);
-                if (member) err = evp_aligned_error(T, p, g) / sc;
-            }
-        }
+        double n;
+        bool kept;
+        const double err = pa_joint_set_error(act && j >= lo && j < hi, w, p, g, sc, n, kept);
         const double esum = wave_reduce_sum_f64(err);
         if (point_err && act) point_err[((size_t)b * 3 + s) * 42 + j] = err;
         if (j == 0) {
@@ -203,6 +212,61 @@ __global__ __launch_bounds__(64) void eval_pa_joints_kernel(const float* __restr
             o[1] = kept ? n : 0.0;
         }
     }
+}
+
+// The transform of one hand's 778 vertices, all valid, by one workgroup of 256: two passes over the mesh (means, centred moments) with
+// `part` (4,10) doubles of LDS between them.  False when var1 == 0 (the set is left out); every thread returns the same T.
+__device__ __forceinline__ bool pa_verts_transform(const float* __restrict__ P, const float* __restrict__ G, double (*part)[10],
+                                                   evp_transform& T) {
+    const int tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
+    double acc[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) acc[k] = 0.0;
+    for (int v = tid; v < NV; v += 256) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { acc[k] += (double)P[3 * v + k]; acc[3 + k] += (double)G[3 * v + k]; }
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const double s = wave_reduce_sum_f64(acc[k]);
+        if (lane == 0) part[wave][k] = s;
+    }
+    __syncthreads();
+    double m1[3], m2[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        m1[k] = (((part[0][k] + part[1][k]) + part[2][k]) + part[3][k]) / (double)NV;
+        m2[k] = (((part[0][3 + k] + part[1][3 + k]) + part[2][3 + k]) + part[3][3 + k]) / (double)NV;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 10; ++k) acc[k] = 0.0;
+    for (int v = tid; v < NV; v += 256) {
+        double x1[3], x2[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { x1[k] = (double)P[3 * v + k] - m1[k]; x2[k] = (double)G[3 * v + k] - m2[k]; }
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[3 * a + c] += x1[a] * x2[c];
+        acc[9] += (x1[0] * x1[0] + x1[1] * x1[1]) + x1[2] * x1[2];
+    }
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+        const double s = wave_reduce_sum_f64(acc[k]);
+        if (lane == 0) part[wave][k] = s;
+    }
+    __syncthreads();
+    double M[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) M[a][c] = ((part[0][3 * a + c] + part[1][3 * a + c]) + part[2][3 * a + c]) + part[3][3 * a + c];
+    const double var1 = ((part[0][9] + part[1][9]) + part[2][9]) + part[3][9];
+    __syncthreads();
+    if (!(var1 > 0.0)) return false;
+    T = procrustes_from_moments((double)NV, m1, m2, M, var1);
+    return true;
 }
 
 // grid = (B, 2), block = 256: one hand's 778 vertices, all valid; the hand counts when mano_params_weight[b][h] > 0.  Three passes over
@@ -217,57 +281,8 @@ __global__ __launch_bounds__(256) void eval_pa_verts_kernel(const float* __restr
     double* pe = point_err ? point_err + ((size_t)b * 2 + h) * NV : nullptr;
     const float* P = (h ? pred_l : pred_r) + (size_t)b * NV3;
     const float* G = (h ? gt_l : gt_r) + (size_t)b * NV3;
-    bool kept = params_weight[b * 2 + h] > 0.f;      // uniform over the block
     evp_transform T;
-    if (kept) {
-        double acc[10];
-#pragma unroll
-        for (int k = 0; k < 10; ++k) acc[k] = 0.0;
-        for (int v = tid; v < NV; v += 256) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { acc[k] += (double)P[3 * v + k]; acc[3 + k] += (double)G[3 * v + k]; }
-        }
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            const double s = wave_reduce_sum_f64(acc[k]);
-            if (lane == 0) part[wave][k] = s;
-        }
-        __syncthreads();
-        double m1[3], m2[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            m1[k] = (((part[0][k] + part[1][k]) + part[2][k]) + part[3][k]) / (double)NV;
-            m2[k] = (((part[0][3 + k] + part[1][3 + k]) + part[2][3 + k]) + part[3][3 + k]) / (double)NV;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 10; ++k) acc[k] = 0.0;
-        for (int v = tid; v < NV; v += 256) {
-            double x1[3], x2[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { x1[k] = (double)P[3 * v + k] - m1[k]; x2[k] = (double)G[3 * v + k] - m2[k]; }
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) acc[3 * a + c] += x1[a] * x2[c];
-            acc[9] += (x1[0] * x1[0] + x1[1] * x1[1]) + x1[2] * x1[2];
-        }
-#pragma unroll
-        for (int k = 0; k < 10; ++k) {
-            const double s = wave_reduce_sum_f64(acc[k]);
-            if (lane == 0) part[wave][k] = s;
-        }
-        __syncthreads();
-        double M[3][3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) M[a][c] = ((part[0][3 * a + c] + part[1][3 * a + c]) + part[2][3 * a + c]) + part[3][3 * a + c];
-        const double var1 = ((part[0][9] + part[1][9]) + part[2][9]) + part[3][9];
-        __syncthreads();
-        kept = var1 > 0.0;
-        if (kept) T = procrustes_from_moments((double)NV, m1, m2, M, var1);
-    }
+    const bool kept = params_weight[b * 2 + h] > 0.f && pa_verts_transform(P, G, part, T);      // uniform over the block
     if (!kept) {
         if (pe) for (int v = tid; v < NV; v += 256) pe[v] = 0.0;
         if (tid == 0) { o[0] = 0.0; o[1] = 0.0; }
@@ -286,4 +301,254 @@ __global__ __launch_bounds__(256) void eval_pa_verts_kernel(const float* __restr
     if (lane == 0) part[wave][0] = s;
     __syncthreads();
     if (tid == 0) { o[0] = ((part[0][0] + part[1][0]) + part[2][0]) + part[3][0]; o[1] = (double)NV; }
+}
+
+// ------------------------------------------------------------------------------------------ curve metrics: PCK counts, F-score counts
+// The other half of a hand-mesh result table: per threshold tau_k the NUMBER of points whose error is <= tau_k (the host divides and
+// integrates: PCK curve and its AUC), and per hand the number of nearest-neighbour distances < tau (precision / recall of the F-score).
+// A point's thresholds are found once -- its threshold index (csrc/eval_pure.h), a binary search over the table in LDS -- and
+// counted into an integer histogram in LDS (integer atomics: the result has no order); the histogram summed from the left is the
+// count per threshold.  Inputs float32, every operation float64, no float atomics, every float sum in one fixed order; a sample's
+// (hand's) result does not depend on its place in the batch.  Counts are written as doubles: they add over batches and ranks with the
+// other metric sums.
+#define EVAL_MAX_T IHMR_EVAL_MAX_THRESHOLDS        // 256
+#define EVAL_MAX_F IHMR_EVAL_MAX_F_THRESHOLDS      // 8
+
+// hist[0..T) in LDS -> out[k] = hist[0] + ... + hist[k] for k < T, out[T] = n.  One whole wave: lane l sums its run of
+// ceil(T / 64) consecutive entries, the runs are scanned over the wave.
+__device__ __forceinline__ void curve_emit_counts(const int* hist, int T, double n, double* __restrict__ out) {
+    const int lane = threadIdx.x % WAVE, per = (T + WAVE - 1) / WAVE, base = lane * per;
+    int local = 0;
+    for (int i = 0; i < per; ++i)
+        if (base + i < T) local += hist[base + i];
+    int incl = local;
+#pragma unroll
+    for (int o = 1; o < WAVE; o <<= 1) {
+        const int v = __shfl_up(incl, o);
+        if (lane >= o) incl += v;
+    }
+    int run = incl - local;
+    for (int i = 0; i < per; ++i)
+        if (base + i < T) { run += hist[base + i]; out[base + i] = (double)run; }
+    if (lane == 0) out[T] = n;
+}
+
+// grid = B, block = 64: lane j < 42 owns joint j.  Three populations per sample:
+//   0  j3d           the valid joints of a hand whose wrist is valid: get_single_joints_error in float64 (root 0 subtracted for the
+//                    right hand, then -- on the already shifted copies -- root 21 for the left)
+//   1  pa_inter_j3d  all valid joints, one alignment (the set 0 of eval_pa_joints_kernel)
+//   2  pa_j3d        the valid joints, one alignment per hand (sets 1 + 2)
+// counts (B,3,T+1) doubles: [#err <= tau_0 .. #err <= tau_{T-1}, number of points].  1 <= T <= EVAL_MAX_T, thresholds ascending.
+__global__ __launch_bounds__(64) void eval_curve_joints_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                               const float* __restrict__ scale, int B,
+                                                               const double* __restrict__ thresholds, int T,
+                                                               double* __restrict__ counts) {
+    __shared__ double thr[EVAL_MAX_T];
+    __shared__ int hist[3][EVAL_MAX_T + 1];
+    const int b = blockIdx.x, j = threadIdx.x;
+    const bool act = j < 42;
+    for (int k = j; k < T; k += 64) thr[k] = thresholds[k];
+    for (int k = j; k < 3 * (EVAL_MAX_T + 1); k += 64) (&hist[0][0])[k] = 0;
+    double p[3] = {0.0, 0.0, 0.0}, g[3] = {0.0, 0.0, 0.0}, w = 0.0;
+    if (act) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { p[k] = (double)pred[((size_t)b * 42 + j) * 3 + k]; g[k] = (double)gt[((size_t)b * 42 + j) * 4 + k]; }
+        w = (double)gt[((size_t)b * 42 + j) * 4 + 3];
+    }
+    const double sc = scale ? (double)scale[b] : 1.0;
+    __syncthreads();
+
+    double n[3] = {0.0, 0.0, 0.0};
+    {   // ---- population 0
+        double a[3] = {p[0], p[1], p[2]}, c[3] = {g[0], g[1], g[2]};
+        bool counted = false;
+        double err = 0.0;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int root = 21 * h;
+            if (__shfl(w, root) > 0.0) {     // uniform over the wave
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { a[k] -= __shfl(a[k], root); c[k] -= __shfl(c[k], root); }
+                if (act && j >= root && j < root + 21 && w > 0.0) {
+                    err = sqrt(evp_sq_dist(a[0], a[1], a[2], c[0], c[1], c[2])) / sc;
+                    counted = true;
+                }
+            }
+        }
+        if (counted) atomicAdd(&hist[0][evp_threshold_index(err, thr, T)], 1);
+        n[0] = wave_reduce_sum_f64(counted ? 1.0 : 0.0);
+    }
+    // ---- populations 1 and 2: the three sets of eval_pa_joints_kernel
+#pragma nounroll
+    for (int s = 0; s < 3; ++s) {
+        const int lo = s == 2 ? 21 : 0, hi = s == 1 ? 21 : 42;
+        const bool in_set = act && j >= lo && j < hi;
+        double ns;
+        bool kept;
+        const double err = pa_joint_set_error(in_set, w, p, g, sc, ns, kept);
+        if (kept) {
+            if (in_set && w > 0.0) atomicAdd(&hist[s == 0 ? 1 : 2][evp_threshold_index(err, thr, T)], 1);
+            if (s == 0) n[1] += ns; else n[2] += ns;
+        }
+    }
+    __syncthreads();
+    double* o = counts + (size_t)b * 3 * (T + 1);
+    curve_emit_counts(hist[0], T, n[0], o);
+    curve_emit_counts(hist[1], T, n[1], o + (T + 1));
+    curve_emit_counts(hist[2], T, n[2], o + 2 * (T + 1));
+}
+
+// The minimum squared distance from each of a thread's query points (slot s = vertex tid + 256 s) to the 778 targets held as three
+// arrays in LDS.  Every lane reads the same target at the same time (a broadcast, no bank conflict) and one read serves all slots.
+// 778 = 3 * 256 + 10: slot 3 exists for tid < 10 only, so only wave 0 walks it (`slot3` is uniform over a wave).
+__device__ __forceinline__ void nn_min_sq(const double (&q)[4][3], const double* tx, const double* ty, const double* tz, bool slot3,
+                                          double (&best)[4]) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) best[s] = INFINITY;
+    for (int j = 0; j < NV; ++j) {
+        const double x = tx[j], y = ty[j], z = tz[j];
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            const double d = evp_sq_dist(q[s][0], q[s][1], q[s][2], x, y, z);
+            best[s] = d < best[s] ? d : best[s];
+        }
+        if (slot3) {
+            const double d = evp_sq_dist(q[3][0], q[3][1], q[3][2], x, y, z);
+            best[3] = d < best[3] ? d : best[3];
+        }
+    }
+}
+
+// grid = (B, 2), block = 256: one hand per workgroup; the hand counts when mano_params_weight[b][h] > 0.
+//   counts   (B,2,2,T+1)    hand, then v3d (root-relative, the root = root_w . mesh, as get_single_verts_error) / pa_v3d (aligned, as
+//                           eval_pa_verts_kernel): [#err <= tau_k ..., number of points]
+//   f_counts (B,2,2,2,F)    hand, raw / pa, p->g / g->p, tau: the number of nearest-neighbour distances < tau  (NULL with F = 0)
+//   nn_dist  (B,2,2,2,778)  the distances themselves, or NULL
+// raw: p = P - root(P), g = G - root(G); pa: p = scale R P + t, g = G.  d_pg[i] = min_j |p_i - g_j| / sc, d_gp[j] = min_i |p_i - g_j| / sc:
+// the minimum over squared distances, one root.  Four passes (raw p->g, raw g->p, pa p->g, pa g->p): the target set of a pass lies in
+// LDS (3 x 778 doubles), each thread keeps its up to four query points in registers; between passes the roles swap.
+// A hand that does not count writes zeros everywhere; a hand the PA rules leave out (var1 == 0) writes zeros in its pa halves.
+__global__ __launch_bounds__(256) void eval_curve_verts_kernel(const float* __restrict__ pred_r, const float* __restrict__ pred_l,
+                                                               const float* __restrict__ gt_r, const float* __restrict__ gt_l,
+                                                               const float* __restrict__ root_w, const float* __restrict__ params_weight,
+                                                               const float* __restrict__ scale, int B,
+                                                               const double* __restrict__ thresholds, int T,
+                                                               const double* __restrict__ f_thresholds, int F,
+                                                               double* __restrict__ counts, double* __restrict__ f_counts,
+                                                               double* __restrict__ nn_dist) {
+    __shared__ double tx[NV], ty[NV], tz[NV];
+    __shared__ double thr[EVAL_MAX_T], fthr[EVAL_MAX_F];
+    __shared__ double part[4][10];
+    __shared__ int hist[2][EVAL_MAX_T + 1];
+    __shared__ int fhist[4][EVAL_MAX_F + 1];
+    const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
+    const size_t hand = (size_t)b * 2 + h;
+    double* o = counts + hand * 2 * (T + 1);
+    double* fo = F > 0 ? f_counts + hand * 4 * F : nullptr;
+    double* nd = nn_dist ? nn_dist + hand * 4 * NV : nullptr;
+    if (!(params_weight[b * 2 + h] > 0.f)) {         // uniform over the block
+        for (int k = tid; k < 2 * (T + 1); k += 256) o[k] = 0.0;
+        for (int k = tid; k < 4 * F; k += 256) fo[k] = 0.0;
+        if (nd) for (int k = tid; k < 4 * NV; k += 256) nd[k] = 0.0;
+        return;
+    }
+    for (int k = tid; k < T; k += 256) thr[k] = thresholds[k];
+    for (int k = tid; k < F; k += 256) fthr[k] = f_thresholds[k];
+    for (int k = tid; k < 2 * (EVAL_MAX_T + 1); k += 256) (&hist[0][0])[k] = 0;
+    for (int k = tid; k < 4 * (EVAL_MAX_F + 1); k += 256) (&fhist[0][0])[k] = 0;
+    const float* P = (h ? pred_l : pred_r) + (size_t)b * NV3;
+    const float* G = (h ? gt_l : gt_r) + (size_t)b * NV3;
+    const float* W = root_w + (size_t)h * NV;
+    const double sc = scale ? (double)scale[b] : 1.0;
+
+    // ---- the two roots, float64: lane-strided partials, butterfly over the wave, waves in index order
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int v = tid; v < NV; v += 256) {
+        const double w = (double)W[v];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { acc[k] += w * (double)P[3 * v + k]; acc[3 + k] += w * (double)G[3 * v + k]; }
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const double s = wave_reduce_sum_f64(acc[k]);
+        if (lane == 0) part[wave][k] = s;
+    }
+    __syncthreads();
+    double rootP[3], rootG[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        rootP[k] = ((part[0][k] + part[1][k]) + part[2][k]) + part[3][k];
+        rootG[k] = ((part[0][3 + k] + part[1][3 + k]) + part[2][3 + k]) + part[3][3 + k];
+    }
+    __syncthreads();
+    evp_transform T_pa;
+    const bool kept_pa = pa_verts_transform(P, G, part, T_pa);      // uniform over the block
+
+    // ---- the two error populations
+    for (int v = tid; v < NV; v += 256) {
+        const double p[3] = {(double)P[3 * v], (double)P[3 * v + 1], (double)P[3 * v + 2]};
+        const double g[3] = {(double)G[3 * v], (double)G[3 * v + 1], (double)G[3 * v + 2]};
+        const double e = sqrt(evp_sq_dist(p[0] - rootP[0], p[1] - rootP[1], p[2] - rootP[2], g[0] - rootG[0], g[1] - rootG[1], g[2] - rootG[2])) / sc;
+        atomicAdd(&hist[0][evp_threshold_index(e, thr, T)], 1);
+        if (kept_pa) atomicAdd(&hist[1][evp_threshold_index(evp_aligned_error(T_pa, p, g) / sc, thr, T)], 1);
+    }
+
+    // ---- the four nearest-neighbour passes
+    if (F > 0 || nd) {
+        // point v of the predicted (which = 0) or the target (which = 1) set of a variant (0 = raw, 1 = pa)
+        auto point = [&](int variant, int which, int v, double* out) {
+            const float* S = which ? G : P;
+            const double x[3] = {(double)S[3 * v], (double)S[3 * v + 1], (double)S[3 * v + 2]};
+            if (variant == 0) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) out[k] = x[k] - (which ? rootG[k] : rootP[k]);
+            } else if (which == 0) {
+                evp_aligned_point(T_pa, x, out);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) out[k] = x[k];
+            }
+        };
+#pragma nounroll
+        for (int pass = 0; pass < 4; ++pass) {
+            const int variant = pass >> 1, dir = pass & 1;       // dir 0: the queries are p, the targets g; dir 1: the reverse
+            if (variant == 1 && !kept_pa) {
+                if (nd) for (int v = tid; v < NV; v += 256) nd[(size_t)pass * NV + v] = 0.0;
+                continue;
+            }
+            __syncthreads();                                     // the pass before has read its targets
+            for (int v = tid; v < NV; v += 256) {
+                double t[3];
+                point(variant, 1 - dir, v, t);
+                tx[v] = t[0]; ty[v] = t[1]; tz[v] = t[2];
+            }
+            double q[4][3], best[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int v = tid + 256 * s;
+                q[s][0] = 0.0; q[s][1] = 0.0; q[s][2] = 0.0;
+                if (v < NV) point(variant, dir, v, q[s]);
+            }
+            __syncthreads();
+            nn_min_sq(q, tx, ty, tz, wave == 0, best);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int v = tid + 256 * s;
+                if (v < NV) {
+                    const double d = sqrt(best[s]) / sc;
+                    if (nd) nd[(size_t)pass * NV + v] = d;
+                    if (F > 0) atomicAdd(&fhist[pass][evp_threshold_index_strict(d, fthr, F)], 1);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (wave == 0) curve_emit_counts(hist[0], T, (double)NV, o);
+    if (wave == 1) curve_emit_counts(hist[1], T, kept_pa ? (double)NV : 0.0, o + (T + 1));
+    if (tid < 4 * F) {
+        const int pass = tid / F, k = tid % F;
+        int c = 0;
+        for (int i = 0; i <= k; ++i) c += fhist[pass][i];
+        fo[(size_t)pass * F + k] = (double)c;
+    }
 }

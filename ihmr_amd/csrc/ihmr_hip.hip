@@ -908,6 +908,26 @@ extern "C" int ihmr_eval_pa_verts(const float* pred_right, const float* pred_lef
     return (int)hipGetLastError();
 }
 
+extern "C" int ihmr_eval_curve_joints(const float* pred_joints_3d, const float* gt_joints_3d, const float* sample_scale, int B,
+                                      const double* thresholds, int T, double* counts, void* stream) {
+    if (!pred_joints_3d || !gt_joints_3d || !thresholds || !counts || B <= 0 || T < 1 || T > IHMR_EVAL_MAX_THRESHOLDS) return -1;
+    hipLaunchKernelGGL(eval_curve_joints_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, pred_joints_3d, gt_joints_3d, sample_scale,
+                       B, thresholds, T, counts);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ihmr_eval_curve_verts(const float* pred_right, const float* pred_left, const float* gt_right, const float* gt_left,
+                                     const float* root_weights, const float* mano_params_weight, const float* sample_scale, int B,
+                                     const double* thresholds, int T, const double* f_thresholds, int F, double* counts,
+                                     double* f_counts, double* nn_dist, void* stream) {
+    if (!pred_right || !pred_left || !gt_right || !gt_left || !root_weights || !mano_params_weight || !thresholds || !counts || B <= 0)
+        return -1;
+    if (T < 1 || T > IHMR_EVAL_MAX_THRESHOLDS || F < 0 || F > IHMR_EVAL_MAX_F_THRESHOLDS || (F > 0 && (!f_thresholds || !f_counts))) return -1;
+    hipLaunchKernelGGL(eval_curve_verts_kernel, dim3(B, 2), dim3(256), 0, (hipStream_t)stream, pred_right, pred_left, gt_right, gt_left,
+                       root_weights, mano_params_weight, sample_scale, B, thresholds, T, f_thresholds, F, counts, f_counts, nn_dist);
+    return (int)hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------ IHMR-MLP training step
 extern "C" int ihmr_mlp_train_grad(const ihmr_mano* m, const ihmr_mano* m_left, const ihmr_opt_io* io, int B,
                                    const ihmr_opt_weights* w, const ihmr_train_weights* tw, const float* gt_pose,

@@ -13,6 +13,12 @@ export GT meshes (IHMR-Baseline / IHMR-MLP; see :func:`get_single_verts_error`).
 the DEVICE tensors of a model (no export to numpy), leaves (B,6) float64 partial results on the device and only
 adds them up when the metrics are asked for -- the per-sample Python loop and the 1 MB/batch device-to-host copies
 of ``get_pred_result()`` drop out of a throughput run.
+
+``Evaluator(curve_metrics=True)`` adds the other half of a hand-mesh result table: the PCK curve (share of points whose error is at most
+tau) and its AUC for five error populations, the mesh F-score at 5 mm / 15 mm and the reference's collision AUC
+(:func:`calc_collision_auc`).  None of them follows from the sums above; all of them follow from COUNTS per threshold, which add over
+batches and ranks (:meth:`Evaluator.curve_sums`, :meth:`Evaluator.curve_metrics_from_sums`).  ``update_device_curves`` /
+``update_device_curve_verts`` count on the GPU (``ihmr_eval_curve_joints`` / ``ihmr_eval_curve_verts``).
 """
 from __future__ import annotations
 
@@ -131,6 +137,97 @@ def get_single_verts_error(pred_verts, gt_verts, root_weights, scale_factor):
     return (np.linalg.norm(pr - gr, axis=1) / scale_factor).tolist()
 
 
+# ------------------------------------------------------------------------------------------ curve metrics: PCK / AUC, F-score, collision AUC
+CURVE_THRESHOLDS = np.linspace(0, 0.05, 100)        # PCK thresholds in the error's units (metres / scale)
+F_THRESHOLDS = (0.005, 0.015)                       # F-score thresholds: 5 mm and 15 mm
+COLLISION_AUC_THRESHOLDS = np.linspace(0.5, 15)     # metric_utils.py:149-153 [mm]
+CURVE_POPULATIONS = ("j3d", "pa_inter_j3d", "pa_j3d", "v3d", "pa_v3d")
+MAX_THRESHOLDS, MAX_F_THRESHOLDS = 256, 8           # include/ihmr_hip.h
+
+
+def calc_collision_auc(collision_all):
+    """metric_utils.py:146-160, operation for operation: the share of samples whose penetration depth [mm] is below a threshold, over
+    ``np.linspace(0.5, 15)``, integrated by the trapezoid rule over the normalised threshold."""
+    col_all = collision_all
+    start = 0.5
+    end = 15
+    xs = list()
+    ratios = list()
+    for thresh in np.linspace(start, end):
+        ratio = np.mean(col_all < thresh)
+        x = (thresh - start) / (end - start)
+        xs.append(x)
+        ratios.append(ratio)
+    return _trapz(ratios, xs)
+
+
+def _trapz(y, x):
+    """``np.trapz`` (``np.trapezoid`` from numpy 2.0 on), the same operations in the same order."""
+    y, x = np.asanyarray(y), np.asanyarray(x)
+    return (np.diff(x) * (y[1:] + y[:-1]) / 2.0).sum()
+
+
+def check_thresholds(thresholds, limit, what="thresholds", allow_empty=False):
+    """A threshold table as float64: 1-D, at most ``limit`` entries, finite and strictly ascending -- else ValueError."""
+    t = np.array(thresholds, dtype=np.float64)
+    if t.ndim != 1 or len(t) > limit or (len(t) == 0 and not allow_empty):
+        raise ValueError(f"{what}: a 1-D table of {0 if allow_empty else 1}..{limit} values is needed, got shape {t.shape}")
+    if not np.isfinite(t).all() or not (np.diff(t) > 0).all():
+        raise ValueError(f"{what} must be finite and strictly ascending")
+    return t
+
+
+def curve_counts(errors, thresholds, strict=False):
+    """(T,) float64: the number of ``errors`` that are <= each threshold (``strict``: < each threshold)."""
+    e, t = np.asarray(errors, np.float64).reshape(-1), np.asarray(thresholds, np.float64)
+    hit = (e[None, :] < t[:, None]) if strict else (e[None, :] <= t[:, None])
+    return hit.sum(axis=1).astype(np.float64)
+
+
+def curve_auc(counts, n, thresholds):
+    """Trapezoid of ``counts / n`` over x_k = (tau_k - tau_0) / (tau_{T-1} - tau_0), the formula of :func:`calc_collision_auc`.
+    NaN without points (n = 0) and for a single threshold."""
+    t = np.asarray(thresholds, np.float64)
+    if not n > 0 or len(t) < 2:
+        return float("nan")
+    return float(_trapz(np.asarray(counts, np.float64) / n, (t - t[0]) / (t[-1] - t[0])))
+
+
+def nn_distances(pred, gt):
+    """Brute-force nearest-neighbour distances between two point sets, float64: ``d_pg[i] = min_j |p_i - g_j|`` and
+    ``d_gp[j] = min_i |p_i - g_j|``.  Every squared distance is ``(dx*dx + dy*dy) + dz*dz``; the minimum is taken on the squares and
+    the root once (min is exact and sqrt monotone: the order of the search cannot change a bit)."""
+    p, g = np.asarray(pred, np.float64), np.asarray(gt, np.float64)
+    d = p[:, None, :] - g[None, :, :]
+    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    return np.sqrt(d2.min(axis=1)), np.sqrt(d2.min(axis=0))
+
+
+def fscore_from_counts(n_pg, n_gp, n):
+    """F = 2 P R / (P + R) with P = n_pg / n, R = n_gp / n; 0 where P + R = 0.  Elementwise over the thresholds."""
+    P, R = np.asarray(n_pg, np.float64) / n, np.asarray(n_gp, np.float64) / n
+    den = P + R
+    return np.where(den > 0, 2.0 * P * R / np.where(den > 0, den, 1.0), 0.0)
+
+
+def get_single_fscore_counts(pred_verts, gt_verts, root_weights, scale, f_thresholds, aligned):
+    """ONE hand: ``(counts (2,F), d_pg, d_gp)`` with ``counts[0][k] = #(d_pg < tau_k)`` and ``counts[1][k] = #(d_gp < tau_k)`` (strict),
+    the distances divided by ``scale``.  ``aligned=False``: both meshes relative to their own root as in
+    :func:`get_single_verts_error`, the difference taken as (P_i - root P) - (G_j - root G).  ``aligned=True``: the prediction mapped
+    onto the target by :func:`procrustes_align`; None when the PA rules leave the hand out."""
+    P, G = np.asarray(pred_verts).astype(np.float64), np.asarray(gt_verts).astype(np.float64)
+    if aligned:
+        p, g = procrustes_align(P, G), G
+        if p is None:
+            return None
+    else:
+        rw = np.asarray(root_weights).astype(np.float64)
+        p, g = P - rw @ P, G - rw @ G
+    d_pg, d_gp = nn_distances(p, g)
+    d_pg, d_gp = d_pg / scale, d_gp / scale
+    return np.stack([curve_counts(d_pg, f_thresholds, strict=True), curve_counts(d_gp, f_thresholds, strict=True)]), d_pg, d_gp
+
+
 def load_image_bgr(path):
     """The default image loader of :meth:`Evaluator.visualize_result`: (H,W,3) uint8 in BGR order, as ``cv2.imread`` returns it."""
     from PIL import Image
@@ -145,8 +242,13 @@ def write_image_bgr(path, img):
 
 
 class Evaluator:
-    def __init__(self, mano_models=None, data_list=None, image_root="", inputSize=224, pa_metrics=False):
+    def __init__(self, mano_models=None, data_list=None, image_root="", inputSize=224, pa_metrics=False, curve_metrics=False,
+                 thresholds=None, f_thresholds=None):
         self.pa_metrics = pa_metrics    # records carry the Procrustes-aligned errors too (off: records and files as before)
+        # records carry what the PCK curves, the F-scores and the collision AUC are counted from (off: records and files as before)
+        self.curve_metrics = curve_metrics
+        self.thresholds = check_thresholds(CURVE_THRESHOLDS if thresholds is None else thresholds, MAX_THRESHOLDS)
+        self.f_thresholds = check_thresholds(F_THRESHOLDS if f_thresholds is None else f_thresholds, MAX_F_THRESHOLDS, "f_thresholds", True)
         self.inputSize = inputSize      # evaluator.py:27 (model.inputSize): the visualisation renders at twice this size by default
         self.left_hand_faces = None if mano_models is None else mano_models["left"].faces
         self.right_hand_faces = None if mano_models is None else mano_models["right"].faces
@@ -163,6 +265,8 @@ class Evaluator:
         self._device_vert_parts = []   # (B,2) float64 [sum of per-vertex errors, count]
         self._device_pa_parts = []     # (B,4) float64 [sum of set 0, count, sum of the per-hand sets, count]
         self._device_pa_vert_parts = []   # (B,2) float64 [sum of aligned per-vertex errors, count]
+        self._device_curve_parts = []     # (B,3,T+1) float64 counts of the joint populations
+        self._device_curve_vert_parts = []   # ((B,2,T+1) counts, (B,2,2,2,F) per-hand F counts, (B,2,2) hand counted and kept)
 
     def clear(self):
         self.pred_results = []
@@ -170,6 +274,68 @@ class Evaluator:
         self._device_vert_parts = []
         self._device_pa_parts = []
         self._device_pa_vert_parts = []
+        self._device_curve_parts = []
+        self._device_curve_vert_parts = []
+
+    def _curve_tables(self, dev):
+        """The two threshold tables on ``dev`` (float64), uploaded once per device."""
+        import torch
+        cached = getattr(self, "_curve_tables_dev", None)
+        if cached is None or cached[0] != dev:
+            t = torch.from_numpy(self.thresholds).to(dev)
+            f = torch.from_numpy(self.f_thresholds).to(dev) if len(self.f_thresholds) else None
+            self._curve_tables_dev = cached = (dev, t, f)
+        return cached[1], cached[2]
+
+    def update_device_curves(self, pred_joints_3d, gt_joints_3d, keep=None, scale=None):
+        """Counts per threshold of the three joint populations of one batch from device tensors (``ihmr_eval_curve_joints``);
+        arguments as :meth:`update_device_pa`.  Accumulates lazily, see :meth:`curve_sums`."""
+        import torch
+
+        from . import hip
+        hip.require_gpu()
+        B, dev = pred_joints_3d.shape[0], pred_joints_3d.device
+        f = lambda t: t.detach().to(dev, torch.float32).contiguous()
+        p, g = f(pred_joints_3d), f(gt_joints_3d)
+        sc = None if scale is None else f(scale)
+        thr, _ = self._curve_tables(dev)
+        T = len(self.thresholds)
+        out = torch.empty(B, 3, T + 1, device=dev, dtype=torch.float64)
+        hip.check(hip.lib().ihmr_eval_curve_joints(p.data_ptr(), g.data_ptr(), None if sc is None else sc.data_ptr(), B, thr.data_ptr(), T,
+                                                   out.data_ptr(), hip.stream_ptr()), "ihmr_eval_curve_joints")
+        if keep is not None:
+            out = out * keep.to(dev, torch.float64)[:, None, None]
+        self._device_curve_parts.append(out)
+
+    def update_device_curve_verts(self, pred_right, pred_left, gt_right, gt_left, mano_params_weight, keep=None, scale=None):
+        """Counts per threshold of the two vertex populations and the per-hand F-scores (raw and aligned) of one batch from device
+        tensors (``ihmr_eval_curve_verts``); arguments as :meth:`update_device_verts`."""
+        import torch
+
+        from . import hip
+        hip.require_gpu()
+        assert self.root_weights is not None, "Evaluator needs the MANO models (J_regressor) for the root-relative vertex errors"
+        B, dev = pred_right.shape[0], pred_right.device
+        f = lambda t: t.detach().to(dev, torch.float32).contiguous()
+        pr, pl, gr, gl, w = f(pred_right), f(pred_left), f(gt_right), f(gt_left), f(mano_params_weight)
+        if not hasattr(self, "_root_w_dev") or self._root_w_dev.device != dev:
+            self._root_w_dev = torch.from_numpy(self.root_weights).to(dev).contiguous()
+        sc = None if scale is None else f(scale)
+        thr, fthr = self._curve_tables(dev)
+        T, F = len(self.thresholds), len(self.f_thresholds)
+        counts = torch.empty(B, 2, 2, T + 1, device=dev, dtype=torch.float64)
+        fc = torch.empty(B, 2, 2, 2, F, device=dev, dtype=torch.float64)
+        hip.check(hip.lib().ihmr_eval_curve_verts(pr.data_ptr(), pl.data_ptr(), gr.data_ptr(), gl.data_ptr(), self._root_w_dev.data_ptr(),
+                                                  w.data_ptr(), None if sc is None else sc.data_ptr(), B, thr.data_ptr(), T,
+                                                  None if fthr is None else fthr.data_ptr(), F, counts.data_ptr(),
+                                                  fc.data_ptr() if F else None, None, hip.stream_ptr()), "ihmr_eval_curve_verts")
+        # the counts stay what they are: F is formed per hand on the host (:func:`fscore_from_counts`, the one formula of both paths)
+        counted = (counts[..., T] > 0).to(torch.float64)                    # (B,2,2): hand, raw / pa
+        csum = counts[:, 0] + counts[:, 1]
+        if keep is not None:
+            k = keep.to(dev, torch.float64)
+            csum, counted = csum * k[:, None, None], counted * k[:, None, None]
+        self._device_curve_vert_parts.append((csum, fc, counted))
 
     def update_device_pa(self, pred_joints_3d, gt_joints_3d, keep=None, scale=None):
         """Procrustes-aligned joint errors of one batch from device tensors (``ihmr_eval_pa_joints``): pred_joints_3d (B,42,3),
@@ -312,9 +478,43 @@ class Evaluator:
                             single["pa_v3d_error"] += get_single_pa_error(pred_results[f"pred_{side}_hand_verts"][i],
                                                                           pred_results[f"gt_{side}_hand_verts"][i],
                                                                           np.ones(len(pred_results[f"pred_{side}_hand_verts"][i])), single["scale"])
+            if getattr(self, "curve_metrics", False):
+                self._add_curve_lists(single, pred_results, i)
             if "do_flip" in pred_results and pred_results["do_flip"][i]:
                 self._flip_back_data(single)
             self.pred_results.append(single)
+
+    NN_KEYS = ("nn_dist_raw_pg", "nn_dist_raw_gp", "nn_dist_pa_pg", "nn_dist_pa_gp")
+
+    def _add_curve_lists(self, single, pred_results, i):
+        """What the curve metrics are counted from: ``curve_j3d_error`` (the float64 form of ``j3d_error``, which keeps its dtype), the
+        PA lists (under the keys of ``pa_metrics``, computed whether or not that flag is set) and, where GT meshes are exported, per
+        counted hand the four nearest-neighbour distance arrays (raw / aligned, p->g / g->p)."""
+        gt, p = single["gt_joints_3d"], single["pred_joints_3d"]
+        single["curve_j3d_error"] = get_single_joints_error(np.asarray(p).astype(np.float64), np.asarray(gt[:, :3]).astype(np.float64),
+                                                            gt[:, 3:], single["scale"])
+        meshes = "gt_right_hand_verts" in pred_results and self.root_weights is not None
+        if not getattr(self, "pa_metrics", False):
+            single["pa_inter_j3d_error"] = get_single_pa_error(p, gt[:, :3], gt[:, 3], single["scale"])
+            single["pa_j3d_error"] = (get_single_pa_error(p[:21], gt[:21, :3], gt[:21, 3], single["scale"])
+                                      + get_single_pa_error(p[21:], gt[21:, :3], gt[21:, 3], single["scale"]))
+            if meshes:
+                single["pa_v3d_error"] = []
+        if not meshes:
+            return
+        for key in self.NN_KEYS:
+            single[key] = []
+        for h, side in enumerate(("right", "left")):
+            if not pred_results["mano_params_weight"][i][h] > 0:
+                continue
+            pv, gv = pred_results[f"pred_{side}_hand_verts"][i], pred_results[f"gt_{side}_hand_verts"][i]
+            if not getattr(self, "pa_metrics", False):
+                single["pa_v3d_error"] += get_single_pa_error(pv, gv, np.ones(len(pv)), single["scale"])
+            for variant, aligned in (("raw", False), ("pa", True)):
+                r = get_single_fscore_counts(pv, gv, self.root_weights[h], single["scale"], self.f_thresholds, aligned)
+                if r is not None:
+                    single[f"nn_dist_{variant}_pg"].append(r[1])
+                    single[f"nn_dist_{variant}_gp"].append(r[2])
 
     def _flip_back_data(self, single):
         """evaluator.py:100-134: a sample that the loader mirrored (left-only image turned into a right hand) goes back to
@@ -388,6 +588,93 @@ class Evaluator:
             import torch
             sums[4:6] = sums[4:6] + torch.cat(self._device_pa_vert_parts, dim=0).sum(dim=0).cpu().numpy()
         return sums
+
+    def curve_sums(self):
+        """One flat float64 vector, additive over batches and ranks.  With T = len(thresholds), F = len(f_thresholds) and the C = 50
+        thresholds of :func:`calc_collision_auc`:
+
+        * 5 blocks of T + 1, the populations ``j3d, pa_inter_j3d, pa_j3d, v3d, pa_v3d``: [#err <= tau_0 .. #err <= tau_{T-1}, n];
+        * 2 blocks of F + 1, ``fscore_raw, fscore_pa``: [sum over the counted hands of the hand's F at tau_0 .. tau_{F-1}, hands];
+        * 2 blocks of C + 1, the per-sample max and mean penetration depth [mm] of the interacting samples:
+          [#x < tau_0 .. #x < tau_{C-1}, n].
+
+        Everything is a count except the F sums: F is formed per hand from that hand's two counts, and the sum over hands is the
+        correctly rounded one (``math.fsum``), so it does not depend on the order or the grouping of the hands.  Records of an
+        ``Evaluator(curve_metrics=True)`` plus what :meth:`update_device_curves` / :meth:`update_device_curve_verts` left on the
+        device and, with ``curve_metrics`` set, the collision columns of :meth:`update_device`."""
+        import math
+        thr, fthr = self.thresholds, self.f_thresholds
+        T, F, nv = len(thr), len(fthr), 778.0
+        recs = [p for p in self.pred_results if "curve_j3d_error" in p]
+        blocks = []
+        for name in CURVE_POPULATIONS:
+            e = [x for p in recs for x in p.get("curve_j3d_error" if name == "j3d" else f"{name}_error", [])]
+            blocks.append(np.concatenate([curve_counts(e, thr), [len(e)]]))
+        fvals = {"raw": [], "pa": []}                      # per variant the per-hand F rows (F,)
+        for variant in ("raw", "pa"):
+            for p in recs:
+                for d_pg, d_gp in zip(p.get(f"nn_dist_{variant}_pg", []), p.get(f"nn_dist_{variant}_gp", [])):
+                    fvals[variant].append(fscore_from_counts(curve_counts(d_pg, fthr, strict=True), curve_counts(d_gp, fthr, strict=True), nv))
+        hands = {v: float(len(fvals[v])) for v in fvals}
+        inter = [p for p in recs if p["hand_type"] == "interacting"]
+        cmax = [[np.max(p["collision_loss_origin_scale"].astype(np.float64)) * 1000 for p in inter]]
+        cave = [[np.mean(p["collision_loss_origin_scale"].astype(np.float64)) * 1000 for p in inter]]
+        n_inter = float(len(inter))
+        if getattr(self, "_device_curve_parts", None):
+            import torch
+            d = torch.cat(self._device_curve_parts, dim=0).sum(dim=0).cpu().numpy()
+            for k in range(3):
+                blocks[k] = blocks[k] + d[k]
+        if getattr(self, "_device_curve_vert_parts", None):
+            import torch
+            parts = self._device_curve_vert_parts
+            d = torch.cat([c for c, _, _ in parts], dim=0).sum(dim=0).cpu().numpy()
+            for k in range(2):
+                blocks[3 + k] = blocks[3 + k] + d[k]
+            counted = torch.cat([c for _, _, c in parts], dim=0).cpu().numpy().reshape(-1, 2)
+            fc = torch.cat([f for _, f, _ in parts], dim=0).cpu().numpy().reshape(len(counted), 2, 2, F)    # (hands, raw / pa, p->g / g->p, F)
+            for k, variant in enumerate(("raw", "pa")):
+                rows = fc[counted[:, k] > 0, k]
+                fvals[variant] += list(fscore_from_counts(rows[:, 0], rows[:, 1], nv))
+                hands[variant] += float(np.sum(counted[:, k] > 0))
+        if self._device_parts and getattr(self, "curve_metrics", False):
+            import torch
+            d = torch.cat(self._device_parts, dim=0)                 # columns 4, 5: mean and max depth [mm]; 6: interacting and kept
+            d = d[d[:, 6] > 0].cpu().numpy()
+            cave.append(d[:, 4])
+            cmax.append(d[:, 5])
+            n_inter += float(len(d))
+        for variant in ("raw", "pa"):
+            rows = np.asarray(fvals[variant], np.float64).reshape(-1, F)
+            blocks.append(np.array([math.fsum(rows[:, k]) for k in range(F)] + [hands[variant]]))
+        for pop in (cmax, cave):
+            blocks.append(np.concatenate([sum(curve_counts(x, COLLISION_AUC_THRESHOLDS, strict=True) for x in pop), [n_inter]]))
+        return np.concatenate(blocks).astype(np.float64)
+
+    @staticmethod
+    def curve_metrics_from_sums(s, thresholds=None, f_thresholds=None):
+        """From a (summed) :meth:`curve_sums` vector: ``pck_<name>`` (T,) and ``auc_<name>`` for the five populations, ``fscore_raw`` /
+        ``fscore_pa`` (F,), ``collision_auc_max`` / ``collision_auc_ave``.  NaN where nothing was counted; an AUC over one threshold
+        is NaN.  The tables are those the sums were counted with (default: the Evaluator's defaults)."""
+        thr = check_thresholds(CURVE_THRESHOLDS if thresholds is None else thresholds, MAX_THRESHOLDS)
+        fthr = check_thresholds(F_THRESHOLDS if f_thresholds is None else f_thresholds, MAX_F_THRESHOLDS, "f_thresholds", True)
+        T, F, C = len(thr), len(fthr), len(COLLISION_AUC_THRESHOLDS)
+        s = np.asarray(s, np.float64)
+        assert len(s) == 5 * (T + 1) + 2 * (F + 1) + 2 * (C + 1), (len(s), T, F)
+        nan = float("nan")
+        out, at = {}, 0
+        for name in CURVE_POPULATIONS:
+            c, n = s[at:at + T], s[at + T]
+            out[f"pck_{name}"] = c / n if n > 0 else np.full(T, nan)
+            out[f"auc_{name}"] = curve_auc(c, n, thr)
+            at += T + 1
+        for name in ("fscore_raw", "fscore_pa"):
+            out[name] = s[at:at + F] / s[at + F] if s[at + F] > 0 else np.full(F, nan)
+            at += F + 1
+        for name in ("collision_auc_max", "collision_auc_ave"):
+            out[name] = curve_auc(s[at:at + C], s[at + C], COLLISION_AUC_THRESHOLDS)
+            at += C + 1
+        return out
 
     @staticmethod
     def pa_metrics_from_sums(s):

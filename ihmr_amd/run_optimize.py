@@ -40,6 +40,11 @@ def main(argv=None):
     ap.add_argument("--pa_metrics", action="store_true",
                     help="also report the Procrustes-aligned joint errors pa_inter_mpjpe_3d (one alignment over both hands) and "
                          "pa_mpjpe_3d (one per hand): on the device (ihmr_eval_pa_joints), from the records under --host_eval")
+    ap.add_argument("--curve_metrics", action="store_true",
+                    help="also report the PCK curves and their AUC of the three joint error populations (j3d, pa_inter_j3d, pa_j3d) "
+                         "and the collision AUCs of the per-sample max / mean penetration depth: counted on the device "
+                         "(ihmr_eval_curve_joints), from the records under --host_eval.  IHMR-OPT exports no GT meshes: no vertex "
+                         "curve, no F-score")
     ap.add_argument("--streams", type=int, default=1,
                     help="model instances driven side by side on their own HIP streams (2 x --fuse_batches 8 saturates one MI355X; "
                          "more than 4 need GPU_MAX_HW_QUEUES raised in the environment)")
@@ -61,7 +66,7 @@ def main(argv=None):
     singles = [model] + [None] * (S - 1)                                      # remainder of fewer than G batches: batch by batch
     main_stream = torch.cuda.current_stream()
     streams = [torch.cuda.Stream() for _ in range(S)] if S > 1 else [main_stream]
-    evaluator = Evaluator(model.mano_models, pa_metrics=args.pa_metrics)
+    evaluator = Evaluator(model.mano_models, pa_metrics=args.pa_metrics, curve_metrics=args.curve_metrics)
     fwd = lambda p, s, t: two_hand.forward_from_packed(model.mano_models["right"], p.cuda(), s.cuda(), t.cuda())[2]
 
     idx, is_pad = D.shard_indices(args.num_samples, args.batchSize, rank, world)
@@ -111,19 +116,29 @@ def main(argv=None):
                                             keep=torch.from_numpy(~pad))
                     if args.pa_metrics:
                         evaluator.update_device_pa(mdl.pred_joints_3d, mdl.buf["gt_joints_3d"], keep=torch.from_numpy(~pad))
+                    if args.curve_metrics:
+                        evaluator.update_device_curves(mdl.pred_joints_3d, mdl.buf["gt_joints_3d"], keep=torch.from_numpy(~pad))
         for _, st, *_ in jobs:
             main_stream.wait_stream(st)                 # the next round's data generation reuses the instances' MANO handles
     torch.cuda.synchronize()
     base = evaluator.metric_sums()
     n_base = len(base)
-    # with --pa_metrics both metric vectors travel in the one all-reduce
-    sums = D.reduce_metrics(np.concatenate([base, evaluator.pa_metric_sums()]) if args.pa_metrics else base)
+    # with --pa_metrics / --curve_metrics all metric vectors travel in the one all-reduce
+    parts = [base] + ([evaluator.pa_metric_sums()] if args.pa_metrics else []) + ([evaluator.curve_sums()] if args.curve_metrics else [])
+    sums = D.reduce_metrics(np.concatenate(parts))
     elapsed = time.time() - t0
     m = Evaluator.metrics_from_sums(sums[:n_base])
+    n_pa = 6 if args.pa_metrics else 0
     if args.pa_metrics:
-        m.update(Evaluator.pa_metrics_from_sums(sums[n_base:]))
+        m.update(Evaluator.pa_metrics_from_sums(sums[n_base:n_base + n_pa]))
+    curve_keys = ()
+    if args.curve_metrics:
+        c = Evaluator.curve_metrics_from_sums(sums[n_base + n_pa:])
+        curve_keys = ("auc_j3d", "auc_pa_inter_j3d", "auc_pa_j3d", "collision_auc_max", "collision_auc_ave")
+        m.update({k: c[k] for k in curve_keys})
+        m.update({k: c[k].tolist() for k in ("pck_j3d", "pck_pa_inter_j3d", "pck_pa_j3d")})       # the curves go into the JSON line
     if rank == 0:
-        for k in ("mpjpe_3d", "inter_mpjpe_3d", "collision_ave", "collision_max") + (("pa_inter_mpjpe_3d", "pa_mpjpe_3d") if args.pa_metrics else ()):
+        for k in ("mpjpe_3d", "inter_mpjpe_3d", "collision_ave", "collision_max") + (("pa_inter_mpjpe_3d", "pa_mpjpe_3d") if args.pa_metrics else ()) + curve_keys:
             print(f"{k} : {m[k]:.3f} (optimize)")
         print(json.dumps(dict(num_samples=args.num_samples, world=world, seconds=elapsed, **m)))
     if torch.distributed.is_available() and torch.distributed.is_initialized():

@@ -326,6 +326,31 @@ int ihmr_eval_pa_joints(const float* pred_joints_3d, const float* gt_joints_3d, 
 int ihmr_eval_pa_verts(const float* pred_right, const float* pred_left, const float* gt_right, const float* gt_left,
                        const float* mano_params_weight, const float* sample_scale, int B, double* out, double* point_err, void* stream);
 
+/* Curve metrics: what the PCK curves, their AUC and the mesh F-scores are formed from, as COUNTS (float64, additive over batches and
+ * ranks; the host divides and integrates).  Every error is float64 arithmetic on the float32 inputs, divided by sample_scale (B)
+ * or NULL (= 1) before it is compared; the set rules of the PA metrics above hold.  thresholds (T) and f_thresholds (F) are DEVICE
+ * pointers to float64 tables, caller-owned, finite and strictly ascending (the library cannot check device contents).
+ *   ihmr_eval_curve_joints  three populations per sample: 0 = j3d (valid joints of a hand whose wrist is valid, root-relative per hand
+ *                           like ihmr_eval_metrics, in float64), 1 = pa_inter_j3d (all valid joints, one alignment), 2 = pa_j3d (one
+ *                           alignment per hand).  counts (B,3,T+1): [#err <= tau_0 .. #err <= tau_{T-1}, number of points].
+ *   ihmr_eval_curve_verts   per hand with mano_params_weight > 0.  counts (B,2,2,T+1): hand, then v3d (root-relative, the root
+ *                           regressed with root_weights (2,778) as in ihmr_eval_mpvpe) / pa_v3d (as ihmr_eval_pa_verts).
+ *                           f_counts (B,2,2,2,F): hand, raw / pa, p->g / g->p, tau: the number of the 778 nearest-neighbour distances
+ *                           that are < tau (strict).  d_pg[i] = min_j |p_i - g_j| / scale, d_gp[j] = min_i |p_i - g_j| / scale, the
+ *                           minimum taken over squared distances (dx*dx + dy*dy) + dz*dz and the root once; raw: p = pred - root(pred),
+ *                           g = gt - root(gt); pa: p = the aligned prediction, g = gt.  nn_dist (B,2,2,2,778) or NULL: the distances.
+ *                           A hand that does not count writes zeros everywhere, one the PA rules leave out zeros in its pa halves.
+ * -1, nothing launched: a NULL required pointer, B <= 0, T < 1, T > IHMR_EVAL_MAX_THRESHOLDS, F < 0, F > IHMR_EVAL_MAX_F_THRESHOLDS,
+ * F > 0 with f_thresholds or f_counts NULL.  No allocation, no synchronisation. */
+#define IHMR_EVAL_MAX_THRESHOLDS 256
+#define IHMR_EVAL_MAX_F_THRESHOLDS 8
+int ihmr_eval_curve_joints(const float* pred_joints_3d, const float* gt_joints_3d, const float* sample_scale, int B,
+                           const double* thresholds, int T, double* counts, void* stream);
+int ihmr_eval_curve_verts(const float* pred_right, const float* pred_left, const float* gt_right, const float* gt_left,
+                          const float* root_weights, const float* mano_params_weight, const float* sample_scale, int B,
+                          const double* thresholds, int T, const double* f_thresholds, int F, double* counts, double* f_counts,
+                          double* nn_dist, void* stream);
+
 /* ------------------------------------------------------------------ packed transfers (round 5)
  * MLPModel.set_input (models/mlp_model.py:120-170) and get_pred_result (:702-719) move 17 + 13 small tensors one copy at a time; one
  * launch does a whole table of them.  A segment = a 2-D strided copy of 32-bit words: dst[r * dst_ld + c] = src[r * src_ld + c] for
