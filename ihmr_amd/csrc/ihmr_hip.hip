@@ -301,7 +301,7 @@ static void lbs_backward_launch(const ihmr_mano* m, bool two_hand, int N, int B,
         hipLaunchKernelGGL(lbs_bwd1_kernel<false>, dim3(N), dim3(LBS_THREADS), part_lds, st, *m, wk, B, d_verts, d_joints, d_orient,
                            d_betas, d_trans, need_mask);
     if (need_mask & 2) {
-        if (plan::bwd2_lds(N, g_bwd2_streaming)) hipLaunchKernelGGL(lbs_bwd2_lds_kernel, dim3((N + 63) / 64, LBS_KG), dim3(320), 0, st, *m, wk, N);
+        if (plan::bwd2_lds(N, g_bwd2_streaming)) hipLaunchKernelGGL(lbs_bwd2_lds_kernel, dim3((N + LBS_B2_HANDS - 1) / LBS_B2_HANDS, LBS_KG), dim3(256), 0, st, *m, wk, N);
         else hipLaunchKernelGGL(lbs_bwd2_kernel, dim3(5, (N + 31) / 32, LBS_KG), dim3(64), 0, st, *m, wk, N);
         if (two_hand) hipLaunchKernelGGL(lbs_bwd3_kernel<true>, dim3(N), dim3(64), 0, st, wk, N, B, d_pose);
         else hipLaunchKernelGGL(lbs_bwd3_kernel<false>, dim3(N), dim3(64), 0, st, wk, N, B, d_pose);
@@ -1316,6 +1316,18 @@ extern "C" int ihmr_debug_tail_stamps(long long* host, int zero) {
     if (zero) { HIP_TRY(hipMemset(p, 0, sizeof(long long) * 3 * 4096 * 8)); HIP_TRY(hipMemset(q, 0, sizeof(long long) * 4096 * 8)); return 0; }
     HIP_TRY(hipMemcpy(host, p, sizeof(long long) * 3 * 4096 * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(host + 3 * 4096 * 8, q, sizeof(long long) * 4096 * 8, hipMemcpyDeviceToHost));      // the sampler's own phases
+    return 0;
+}
+#endif
+
+#ifdef BWD2_STAMPS
+// experiment builds only (scripts/bwd2_stamps.py): zero = 1 clears, zero = 0 copies the 1024 x 8 phase sums of lbs_bwd2_lds_kernel out
+extern "C" int ihmr_debug_bwd2_stamps(long long* host, int zero) {
+    HIP_TRY(hipDeviceSynchronize());
+    void* p;
+    HIP_TRY(hipGetSymbolAddress(&p, HIP_SYMBOL(g_bwd2_stamps)));
+    if (zero) { HIP_TRY(hipMemset(p, 0, sizeof(long long) * 1024 * 8)); return 0; }
+    HIP_TRY(hipMemcpy(host, p, sizeof(long long) * 1024 * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 #endif

@@ -15,8 +15,9 @@
 //           so the basis is streamed from L2 N/8 times instead of N times.
 //   bwd1  : one workgroup per hand -- d v_posed, the 16x12 transform gradients as fixed-order CSR-by-joint
 //           sums, chain backward by tree level, orient / shape / translation gradients.
-//   bwd2  : (finger-pose stage only) d pose_feature = posedirs . d v_posed as an LDS-tiled product,
-//           workgroup = 8 hands x 192 basis columns, partial sums per column chunk (deterministic).
+//   bwd2  : (finger-pose stage only) d pose_feature = posedirs . d v_posed on the f32 matrix cores, from 256 hands on as
+//           an LDS-tiled product, workgroup = four waves x 32 hands x 96 basis columns, partial sums per column group
+//           (deterministic).
 //   bwd3  : (finger-pose stage only) chunk reduction + Rodrigues backward.
 #pragma once
 #include "ihmr_common.h"
@@ -1047,89 +1048,144 @@ __global__ __launch_bounds__(64) void lbs_bwd2_kernel(ihmr_mano m, LbsWork wk, i
     }
 }
 
-// The same GEMM with its operands staged through LDS (round 3).  A workgroup = five waves, one per 32-feature tile, x 64 hands, for one K
-// group: the 32 x (160 + 64) operand block of a 32-column chunk is loaded with the lanes ALONG k (8 lanes = 128 contiguous bytes of a
-// row; the streaming form above has every lane on a row of its own, i.e. 64 cache lines per load instruction -- bound by address
-// processing) and stored row-major with a row stride of 33 floats, so that the MFMA operand reads (lanes along the rows) hit 32
-// different banks; chunks double-buffered.  Same partial layout, same k -> MFMA step assignment (lane half l / 32 owns 16 consecutive
-// columns): the same bits as the streaming form.  grid = (ceil(N/64), LBS_KG), block = 320.
+// The same GEMM with its operands staged through LDS (round 3; rebuilt on whole SIMDs since).  A work unit = 32 hands x one K
+// group x ALL 135 features; a workgroup = four waves = one unit.  Wave w owns the full 32-feature tile w (one v_mfma_f32_32x32x2_f32
+// accumulator, 16 steps per 32-column chunk); the seven leftover features 128..134 are a 16-row tile on v_mfma_f32_16x16x4_f32 (rows
+// 135..143 of it are zero operands), one 16-hand half of the unit each for waves 2 and 3, 8 steps per chunk interleaved with the
+// wave's 32-row steps.  Both instructions are a k-ordered fmaf chain; the four k values of a 16x16x4 step are fed in the order the
+// 32x32x2 chain meets them (lane half l / 32 owns 16 consecutive columns: k0, k0 + 16, k0 + 1, k0 + 17, ...), i.e. lane group g = l / 16
+// reads column 16 (g & 1) + 2 t + (g >> 1) at step t -- the same bits as the streaming form for every feature.
+// The operand block of a chunk, 32 x (128 + 32 + 8) floats, is loaded with the lanes ALONG k (8 lanes = 128 contiguous bytes of a row;
+// the streaming form has every lane on a row of its own, 64 cache lines per load instruction) from clamped addresses, masked in
+// registers, and stored row-major with a row stride of 33 floats, so that the MFMA operand reads (lanes along the rows) hit 32
+// different banks; chunks double-buffered.  The accumulators leave through LDS (the chunk buffers are free by then): a unit's
+// part[kg][h0 .. h0 + 31][0 .. 135] is ONE contiguous run of 17 KB, written as 16-byte pieces with the lanes along it (the
+// accumulator layout has the lanes along the hands: 64 cache lines per store instruction, 544 bytes apart).
+// Load of the matrix cores: 48 32-row steps (64 cycles each) per wave and unit, + 24 16-row steps (32 cycles) on two of the four
+// SIMDs.  grid = (ceil(N/32), LBS_KG) = 600 workgroups at 768 hands, 700 at 896, on 256 CUs with three resident per CU (44 KB of LDS
+// each, one wave per SIMD each): all of them resident at once, the busiest SIMD carries three units = 3 x (48 x 64 + 24 x 32) = 11.5 k
+// cycles = 4.8 us at 2.4 GHz at both sizes, against 2.34 / 2.73 units on average and the 4.4 us of the old form's MFMAs spread evenly
+// (the old form: five waves per workgroup on four SIMDs, the fifth multiplying 25 rows of padding; its busiest SIMD ran three waves'
+// 96 steps back to back, 7.7 us).  Measured at 896 hands: 21.9 -> 13.7 us per launch; a workgroup lives 9.1 us, of which 2.4 are its
+// MFMAs, 2.5 the first chunk's way to LDS, 3.4 waiting for the next chunk, its LDS stores and the chunk barriers, 0.8 the epilogue
+// (-DBWD2_STAMPS, scripts/bwd2_stamps.py; docs/experiments.md -- also for the form that requests all three chunks up front: slower).
 #ifndef LBS_B2_MIN_HANDS
 #define LBS_B2_MIN_HANDS 256
 #endif
 #define LBS_B2_LDK 33
-#define LBS_B2_ROWS (160 + 64)
-__global__ __launch_bounds__(320) void lbs_bwd2_lds_kernel(ihmr_mano m, LbsWork wk, int N) {
+#define LBS_B2_HANDS 32                   // hands per work unit
+#define LBS_B2_ROWS (128 + LBS_B2_HANDS + 8)   // features 0..127 | hands | features 128..135 (135 = zero)
+#define LBS_B2_OLD 140                    // row stride of the transposed output tile [hand][136] (16-byte rows, 12 banks apart)
+typedef float lbs_f32x4 __attribute__((ext_vector_type(4)));
+// Phase stamps (experiment builds only, -DBWD2_STAMPS; scripts/bwd2_stamps.py): shader-clock time of each phase of a workgroup, thread 0,
+// summed in registers and written once at the end
+#ifdef BWD2_STAMPS
+__device__ long long g_bwd2_stamps[1024][8];   // first load -> first barrier | MFMAs | wait for the next chunk + LDS store | barrier | epilogue: to LDS | stores | - | launches
+#define BWD2_TK(k) do { const long long now_ = (long long)__builtin_readcyclecounter(); tk_[k] += now_ - tk_prev_; tk_prev_ = now_; } while (0)
+#else
+#define BWD2_TK(k)
+#endif
+__global__ __launch_bounds__(256) void lbs_bwd2_lds_kernel(ihmr_mano m, LbsWork wk, int N) {
     TL_SCOPE(8);
-    __shared__ float tile[2][LBS_B2_ROWS][LBS_B2_LDK];
-    const int tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE, l31 = lane & 31, kp = lane >> 5;
-    const int h0 = blockIdx.x * 64, kg = blockIdx.y;
-    // loader: unit u = tid + 320 i, i < 6 (1792 of 1920 slots used): row = u / 8 (0..159 features, 160..223 hands), 4 columns at 4 (u % 8)
-    float v4[6][4];
+    __shared__ __attribute__((aligned(16))) float tile[2][LBS_B2_ROWS][LBS_B2_LDK];
+    static_assert(LBS_B2_HANDS * LBS_B2_OLD <= 2 * LBS_B2_ROWS * LBS_B2_LDK, "the output tile reuses the chunk buffers");
+    const int tid = threadIdx.x, lane = tid % WAVE, l31 = lane & 31, kp = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);        // (wave-uniform: the branches on it below are scalar)
+    const int h0 = blockIdx.x * LBS_B2_HANDS, kg = blockIdx.y;
+#ifdef BWD2_STAMPS
+    long long tk_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tk_prev_ = (long long)__builtin_readcyclecounter();
+#endif
+    // loader: slot u = tid + 256 i, i < 5: LDS row u / 8 (0..127 features, 128..159 hands), 4 columns at 4 (u % 8); wave 0 also takes
+    // slot 5: LDS rows 160..167 = features 128..135.  Every slot loads 16 bytes from a clamped address; what lies outside the operands
+    // (e >= 135, hand >= N, k >= 2334) becomes zero in registers.  NV3 % 4 == 2: the last group of four of a row is half valid; it is
+    // loaded from NV3 - 4 (shifted by two), so its valid elements sit in .z, .w
+    typedef float lbs_f4u __attribute__((ext_vector_type(4), aligned(4)));
+    const float* srow[6];
+    bool sok[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const int row = (tid + 256 * i) >> 3;
+        if (row < 128) { srow[i] = m.posedirs + (size_t)row * NV3; sok[i] = true; }
+        else if (row < 128 + LBS_B2_HANDS) { const int h = h0 + row - 128; srow[i] = wk.dvp + (size_t)min(h, N - 1) * NV3; sok[i] = h < N; }
+        else { const int e = row - LBS_B2_HANDS; srow[i] = m.posedirs + (size_t)min(e, NPF - 1) * NV3; sok[i] = e < NPF; }
+    }
+    lbs_f4u v4[6];
     auto load_chunk = [&](int c) {
-        const int k0 = (kg * LBS_KC + c) * 32;
+        const int k = (kg * LBS_KC + c) * 32 + 4 * (tid & 7), kc = min(k, NV3 - 4);
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+            if (i < 5 || wave == 0) v4[i] = *reinterpret_cast<const lbs_f4u*>(srow[i] + kc);
+    };
+    auto store_chunk = [&](int buf, int c) {
+        const int k = (kg * LBS_KC + c) * 32 + 4 * (tid & 7);
+        const bool sh = k + 4 > NV3 && k < NV3;
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
-            const int u = tid + 320 * i, row = u >> 3, k = k0 + 4 * (u & 7);
-            v4[i][0] = v4[i][1] = v4[i][2] = v4[i][3] = 0.f;
-            if (row >= LBS_B2_ROWS) continue;
-            const bool is_a = row < 160;
-            const int r = is_a ? row : h0 + (row - 160);
-            if (is_a ? r >= NPF : r >= N) continue;
-            const float* src = (is_a ? m.posedirs + (size_t)r * NV3 : wk.dvp + (size_t)r * NV3) + k;
-            if (k + 3 < NV3) {
-                typedef float lbs_f4u __attribute__((ext_vector_type(4), aligned(4)));
-                const lbs_f4u x = *reinterpret_cast<const lbs_f4u*>(src);
-                v4[i][0] = x.x; v4[i][1] = x.y; v4[i][2] = x.z; v4[i][3] = x.w;
-            } else {
+            if (i == 5 && wave != 0) continue;
+            const float x[4] = {sh ? v4[i].z : v4[i].x, sh ? v4[i].w : v4[i].y, v4[i].z, v4[i].w};
+            float* dst = &tile[buf][(tid + 256 * i) >> 3][4 * (tid & 7)];
 #pragma unroll
-                for (int t = 0; t < 4; ++t) v4[i][t] = k + t < NV3 ? src[t] : 0.f;
-            }
+            for (int t = 0; t < 4; ++t) dst[t] = (sok[i] && k + t < NV3) ? x[t] : 0.f;
         }
     };
-    auto store_chunk = [&](int buf) {
+    lbs_f32x16 acc;
+    lbs_f32x4 acc7 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const int u = tid + 320 * i, row = u >> 3, kq = 4 * (u & 7);
-            if (row >= LBS_B2_ROWS) continue;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) tile[buf][row][kq + t] = v4[i][t];
-        }
-    };
-    lbs_f32x16 acc0, acc1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    const int g16 = lane >> 4, l15 = lane & 15;
     load_chunk(0);
-    store_chunk(0);
+    store_chunk(0, 0);
     __syncthreads();
+    BWD2_TK(0);
 #pragma unroll 1
     for (int c = 0; c < LBS_KC; ++c) {
         const int cur = c & 1;
         if (c + 1 < LBS_KC) load_chunk(c + 1);               // in flight during the MFMAs below
         const float* arow = &tile[cur][wave * 32 + l31][16 * kp];
-        const float* b0row = &tile[cur][160 + l31][16 * kp];
-        const float* b1row = &tile[cur][160 + 32 + l31][16 * kp];
+        const float* brow = &tile[cur][128 + l31][16 * kp];
+        if (wave >= 2) {
+            const float* a7row = &tile[cur][128 + LBS_B2_HANDS + (l15 & 7)][16 * (g16 & 1) + (g16 >> 1)];
+            const float* b7row = &tile[cur][128 + 16 * (wave - 2) + l15][16 * (g16 & 1) + (g16 >> 1)];
 #pragma unroll
-        for (int st = 0; st < 16; ++st) {
-            const float a = arow[st], b0 = b0row[st], b1 = b1row[st];
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, acc1, 0, 0, 0);
+            for (int t = 0; t < 8; ++t) {
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(arow[2 * t], brow[2 * t], acc, 0, 0, 0);
+                const float a7 = l15 < 8 ? a7row[2 * t] : 0.f;
+                acc7 = __builtin_amdgcn_mfma_f32_16x16x4f32(a7, b7row[2 * t], acc7, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(arow[2 * t + 1], brow[2 * t + 1], acc, 0, 0, 0);
+            }
+        } else {
+#pragma unroll
+            for (int st = 0; st < 16; ++st) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(arow[st], brow[st], acc, 0, 0, 0);
         }
-        if (c + 1 < LBS_KC) store_chunk(cur ^ 1);            // the other buffer: its readers finished before the previous barrier
+        BWD2_TK(1);
+        if (c + 1 < LBS_KC) store_chunk(cur ^ 1, c + 1);     // the other buffer: its readers finished before the previous barrier
+        BWD2_TK(2);
         __syncthreads();
+        BWD2_TK(3);
     }
-    // C/D layout: column (hand) = lane & 31, row (feature) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+    // C/D layouts: 32x32: column (hand) = lane & 31, row (feature) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5); 16x16: column = lane & 15,
+    // row = 4 (lane >> 4) + r.  Every reader of the chunk buffers is past the loop's last barrier.
+    float* out = &tile[0][0][0];                             // [LBS_B2_HANDS][LBS_B2_OLD]
 #pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        const int hand = h0 + 32 * half + l31;
-        if (hand >= N) continue;
-        const lbs_f32x16& acc = half ? acc1 : acc0;
-        float* dst = wk.dpf_part + ((size_t)kg * N + hand) * 136 + wave * 32 + 4 * kp;
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-            const int e4 = wave * 32 + 4 * kp + 8 * r4;
-            if (e4 + 3 < 136) *reinterpret_cast<float4*>(dst + 8 * r4) = make_float4(acc[4 * r4], acc[4 * r4 + 1], acc[4 * r4 + 2], acc[4 * r4 + 3]);
+    for (int r4 = 0; r4 < 4; ++r4)
+        *reinterpret_cast<float4*>(out + l31 * LBS_B2_OLD + wave * 32 + 4 * kp + 8 * r4) = make_float4(acc[4 * r4], acc[4 * r4 + 1], acc[4 * r4 + 2], acc[4 * r4 + 3]);
+    if (wave >= 2 && g16 < 2)
+        *reinterpret_cast<float4*>(out + (16 * (wave - 2) + l15) * LBS_B2_OLD + 128 + 4 * g16) = make_float4(acc7[0], acc7[1], acc7[2], acc7[3]);
+    __syncthreads();
+    BWD2_TK(4);
+    const int n4 = min(LBS_B2_HANDS, N - h0) * 34;          // 16-byte pieces of this unit's rows of part[kg]: one contiguous run
+    float4* dst = reinterpret_cast<float4*>(wk.dpf_part + ((size_t)kg * N + h0) * 136);
+    for (int i = tid; i < n4; i += 256) dst[i] = *reinterpret_cast<const float4*>(out + (i / 34) * LBS_B2_OLD + 4 * (i % 34));
+#ifdef BWD2_STAMPS
+    BWD2_TK(5);
+    if (tid == 0) {
+        const int wg = blockIdx.y * gridDim.x + blockIdx.x;
+        if (wg < 1024) {
+            for (int k = 0; k < 6; ++k) g_bwd2_stamps[wg][k] += tk_[k];
+            g_bwd2_stamps[wg][7] += 1;
         }
     }
+#endif
 }
 
 // ------------------------------------------------------------------------------------- backward 3
