@@ -23,7 +23,7 @@ from . import mano as mano_shim
 from . import ry_utils
 from .baseline_train import BaselineTrainMixin
 from .networks import InterHandEncoder
-from .sdf import SDFLoss
+from .sdf import SDFLoss, refuse_training_robustifier
 
 TIP_IDS = (744, 320, 443, 554, 671)  # baseline_model.py:136
 
@@ -45,6 +45,7 @@ class InterHandModel(BaselineTrainMixin):
         # inference only: the training step differentiates the fp32 kernels
         if self.isTrain and getattr(opt, "encoder_precision", "fp32") != "fp32":
             raise ValueError("encoder_precision = %r is an inference option; training runs in fp32 (isTrain = True)" % (opt.encoder_precision,))
+        refuse_training_robustifier(opt)
         self.inputSize = opt.inputSize
         self.batch_size = opt.batchSize
         self.cam_params_dim, self.pose_params_dim = opt.cam_params_dim, opt.pose_params_dim

@@ -74,8 +74,9 @@ class BaselineTrainMixin:
     def forward_train(self):
         self.final_params, self.pred_hand_type = self.trainer.forward(self.input_img)
 
-    # baseline_model.py:285-347
-    def optimize_parameters(self):
+    # baseline_model.py:285-341 up to loss.backward(): fills _grad122 = d loss / d final_params, _d_hand = d loss / d pred_hand_type,
+    # _terms5 and the core's loss_batch from self.final_params (B,122) and self.pred_hand_type (B,2), whoever assigned them
+    def compute_loss_gradients(self):
         core, B, w = self._core, self.batch_size, self.loss_weights
         io, c = core.io, core.buf
         c["gt_joints_2d"].copy_(self.joints_2d)
@@ -99,6 +100,10 @@ class BaselineTrainMixin:
         # torch's binary_cross_entropy backward forms it, (s - t) / max(s (1 - s), 1e-12): finite when the fp32 sigmoid saturates
         # (s == 0 or 1 exactly), where the plain quotient -(t / s - (1 - t) / (1 - s)) is 0/0
         self._d_hand = hand_type_bce_grad(self.pred_hand_type, self.hand_type_array, self.hand_type_valid)
+
+    # baseline_model.py:344-347
+    def optimize_parameters(self):
+        self.compute_loss_gradients()
         self.trainer.backward(self._grad122, self._d_hand)
         self.trainer.optimizer_step(self.world_size)
 

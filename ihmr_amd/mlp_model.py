@@ -25,6 +25,7 @@ from . import hip, two_hand
 from .networks import InterHandSubNetwork
 from .mlp_train import MLPTrainMixin
 from .optimize_model import OptimizeModel
+from .sdf import refuse_training_robustifier
 
 PARAM_DIMS = OrderedDict(pred_hand_trans=3, pred_left_orient=3, pred_right_orient=3, pred_left_pose_params=45,
                          pred_right_pose_params=45, pred_left_shape_params=10, pred_right_shape_params=10, pred_cam_params=3)
@@ -40,6 +41,7 @@ class MLPModel(MLPTrainMixin):
 
     def __init__(self, opt):
         hip.require_gpu()
+        refuse_training_robustifier(opt)
         self.opt = opt
         self.inputSize, self.batch_size = opt.inputSize, opt.batchSize
         self.save_dir = getattr(opt, "checkpoints_dir", "./checkpoints")

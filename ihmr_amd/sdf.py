@@ -17,6 +17,15 @@ import torch.nn as nn
 from . import hip
 
 
+def refuse_training_robustifier(opt):
+    """The reference builds its train-mode collision module with ``robustifier = opt.sdf_robustifier`` (``loss_utils.py:36``); the fused
+    training launches here (``ihmr_mlp_train_grad``) evaluate the collision term with the robustifier off.  Its default is ``None``; a
+    training run that sets it would silently optimise another objective, so it is refused."""
+    if getattr(opt, "isTrain", False) and getattr(opt, "sdf_robustifier", None) is not None:
+        raise ValueError("sdf_robustifier = %r: the training steps evaluate the collision term without a robustifier (isTrain = True); "
+                         "leave it at None" % (opt.sdf_robustifier,))
+
+
 class _SdfFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hand_verts, module):

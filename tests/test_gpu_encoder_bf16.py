@@ -248,7 +248,8 @@ def _seeded(model, seed=100):
 def test_model_switch_graph_replay_keys_and_no_leak(mano_arrays):
     """InterHandModel with encoder_precision = "bf16": test() through the captured graph equals the eager bf16 run bit for bit;
     get_pred_result() has the keys, shapes and dtypes of the fp32 model; an fp32 encoder built afterwards in the same process still
-    meets the bounds of test_encoder_matches_reference_golden; training + bf16 and an unknown precision name are refused."""
+    meets the bounds of test_encoder_matches_reference_golden; training + bf16 and an unknown precision name are refused, and so is
+    training with an sdf_robustifier (by InterHandModel and MLPModel)."""
     from ihmr_amd import two_hand
     from ihmr_amd.baseline_model import InterHandModel
     from ihmr_amd.synthetic import synthetic_opt_batch
@@ -287,6 +288,12 @@ def test_model_switch_graph_replay_keys_and_no_leak(mano_arrays):
         InterHandModel(_opt(B, isTrain=True, encoder_precision="bf16"))
     with pytest.raises(ValueError):
         InterHandModel(_opt(B, encoder_precision="fp16"))
+    # the reference's train-mode robustifier (loss_utils.py:36) is not what the training launches evaluate: refused, by both trainable models
+    from ihmr_amd.mlp_model import MLPModel
+    for cls in (InterHandModel, MLPModel):
+        with pytest.raises(ValueError, match="sdf_robustifier"):
+            cls(_opt(B, isTrain=True, sdf_robustifier=0.05))
+    InterHandModel(_opt(B, sdf_robustifier=0.05))             # inference never reads it
 
 
 def test_report_what_bf16_costs_downstream(mano_arrays):

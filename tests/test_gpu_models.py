@@ -290,8 +290,8 @@ def test_baseline_model_matches_oracle(mano_arrays, B):
     from ihmr_amd.baseline_model import InterHandModel
     from ihmr_amd.synthetic import synthetic_opt_batch
     from oracle import losses_ref as L
+    from baseline_train_ref import separate_two_hand_forward
     from oracle.encoder_ref import InterHandEncoderRef
-    from oracle.mano_ref import ManoRef
     from oracle.sdf_ref import SDFLossRef
     right, left = mano_arrays
     model = InterHandModel(_opt(B))
@@ -304,17 +304,7 @@ def test_baseline_model_matches_oracle(mano_arrays, B):
     ref_enc.eval()
     model.encoder.load_state_dict(sd)
     model.eval()
-    mr = ManoRef(right)
-    l_arr = dict(left); l_arr["shapedirs"] = left["shapedirs"].copy(); l_arr["shapedirs"][:, 0, :] *= -1
-    ml = ManoRef(l_arr)
-
-    def two(pose, shape, trans):
-        outs = {}
-        for name, m, ps, bs in (("right", mr, 0, 0), ("left", ml, 48, 10)):
-            o = m(global_orient=pose[:, ps:ps + 3], hand_pose=pose[:, ps + 3:ps + 48], betas=shape[:, bs:bs + 10])
-            outs[name] = (o.vertices, torch.cat([o.joints, o.vertices[:, [744, 320, 443, 554, 671]]], 1))
-        shift = trans.reshape(-1, 1, 3) + (outs["right"][1][:, 0:1] - outs["left"][1][:, 0:1])
-        return outs["right"][0], outs["left"][0] + shift, torch.cat([outs["right"][1], outs["left"][1] + shift], 1)
+    two = separate_two_hand_forward(mano_arrays)        # the Baseline's own forward: separate right / left models, no mirroring
 
     batch = synthetic_opt_batch(B, lambda p, s, t: two(p, s, t)[2], seed=99, with_image=True)
     model.set_input(batch)
