@@ -4,14 +4,8 @@
 #include <stdint.h>
 
 #include "../../include/ihmr_hip.h"
+#include "mano_tables.h"      // NV, NF, NJ, NV3, NPF, NFP, NVP, LBS_SEG, LBS_SEG_CAP and the host side of struct ihmr_mano below
 
-#define NV IHMR_NUM_VERTS      // 778
-#define NF IHMR_NUM_FACES      // 1538
-#define NJ IHMR_NUM_JOINTS     // 16
-#define NV3 (NV * 3)           // 2334
-#define NPF 135                // pose-feature length (15 joints x 9)
-#define NFP 1600               // faces padded to a multiple of 64 (SoA row length)
-#define NVP 832                // vertices padded to a multiple of 64 (float4 basis rows)
 #define SDF_G IHMR_SDF_GRID    // 32
 #define SDF_NVOX (SDF_G * SDF_G * SDF_G)
 #define WAVE 64

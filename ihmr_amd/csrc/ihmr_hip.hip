@@ -56,174 +56,94 @@ static int timed_next(hipEvent_t* cur, int k, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------ model
-template <typename T>
-static int upload(T** dst, const std::vector<T>& src) {
-    HIP_TRY(hipMalloc((void**)dst, src.size() * sizeof(T)));
-    HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+// Every device buffer of ihmr_mano with the host table it is filled from (mano_tables.h): the ONE list that create, destroy and
+// nothing else walk.  f(device pointer, host data, bytes) -> 0 or an error, which ends the walk.
+template <typename F>
+static int mano_buffers(ihmr_mano& m, const ManoTables& t, F f) {
+    int rc = 0;
+    auto go = [&](auto*& dev, const auto& host) { if (!rc) rc = f((void**)&dev, (const void*)host.data(), host.size() * sizeof(host[0])); };
+    go(m.pd4, t.pd4); go(m.sd4, t.sd4); go(m.vt4, t.vt4);
+    go(m.v_template, t.v_template); go(m.shapedirs_t, t.shapedirs_t); go(m.posedirs, t.posedirs);
+    go(m.J_template, t.J_template); go(m.J_shapedirs, t.J_shapedirs); go(m.weights, t.weights);
+    go(m.w4_w, t.w4_w); go(m.w4_j, t.w4_j);
+    go(m.pose_mean, t.pose_mean); go(m.parents, t.parents); go(m.depth, t.depth);
+    go(m.tip_ids, t.tip_ids); go(m.wj_start, t.wj_start); go(m.wj_vert, t.wj_vert);
+    go(m.wj_w, t.wj_w); go(m.seg_q, t.seg_q); go(m.jseg_start, t.jseg_start);
+    go(m.faces, t.faces); go(m.faces_pk, t.faces_pk); go(m.J_regressor, t.J_regressor);
+    return rc;
+}
+
+// lbs_bwd1 keeps the per-segment partial sums in dynamic LDS (48 B per segment on top of ~36 KB static): dense
+// weight matrices (up to ~960 segments) go past the default 64 KB per workgroup, so raise the cap to what is needed --
+// for every instantiation that is launched with dynamic LDS, and checked: a kernel whose static + dynamic LDS does not fit
+// the device is never launched (m->tail_fits = 0: ihmr_opt_run_stage falls back to the three separate launches)
+static int mano_lds_fit(ihmr_mano* m) {
+    const int dyn = m->nseg * 12 * (int)sizeof(float);
+    hipError_t e1 = hipFuncSetAttribute((const void*)lbs_bwd1_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
+    hipError_t e2 = hipFuncSetAttribute((const void*)lbs_bwd1_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
+    if (e1 != hipSuccess || e2 != hipSuccess) return (int)(e1 != hipSuccess ? e1 : e2);
+    int dev = 0, lds_max = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+    // (opt_tail_kernel_trans has no dynamic LDS: it is checked like the others and asks for none)
+    const void* tails[4] = {(const void*)opt_tail_kernel<true, true>, (const void*)opt_tail_kernel<true>, (const void*)opt_tail_kernel<false>,
+                            (const void*)opt_tail_kernel_trans};
+    m->tail_fits = 1;
+    const int tail_dyn = opt_tail_dynamic_lds(m->nseg);
+    for (const void* k : tails) {
+        hipFuncAttributes fa;
+        const int dyn_k = k == (const void*)opt_tail_kernel_trans ? 0 : tail_dyn;
+        if (hipFuncGetAttributes(&fa, k) != hipSuccess || (long)fa.sharedSizeBytes + dyn_k > (long)lds_max ||
+            (dyn_k && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, dyn_k) != hipSuccess))
+            m->tail_fits = 0;
+    }
+    (void)hipGetLastError();
     return 0;
 }
 
-static void derive_shape_constants(const float* Jreg, const float* v_template, const float* shapedirs,
-                                   std::vector<float>& sd_t, std::vector<float>& J_t, std::vector<float>& J_sd) {
-    sd_t.assign((size_t)10 * NV3, 0.f);
-    for (int v = 0; v < NV; ++v)
-        for (int k = 0; k < 3; ++k)
-            for (int l = 0; l < 10; ++l) sd_t[(size_t)l * NV3 + 3 * v + k] = shapedirs[(v * 3 + k) * 10 + l];
-    J_t.assign(48, 0.f);
-    J_sd.assign(480, 0.f);
-    for (int j = 0; j < NJ; ++j)
-        for (int k = 0; k < 3; ++k) {
-            double acc = 0.0;
-            for (int v = 0; v < NV; ++v) acc += (double)Jreg[j * NV + v] * (double)v_template[3 * v + k];
-            J_t[j * 3 + k] = (float)acc;
-            for (int l = 0; l < 10; ++l) {
-                double a2 = 0.0;
-                for (int v = 0; v < NV; ++v) a2 += (double)Jreg[j * NV + v] * (double)shapedirs[(v * 3 + k) * 10 + l];
-                J_sd[(j * 3 + k) * 10 + l] = (float)a2;
-            }
-        }
-}
-
-static void pack4(const float* src_rows /*[rows][2334]*/, int rows, std::vector<float>& dst) {
-    dst.assign((size_t)rows * NVP * 4, 0.f);
-    for (int r = 0; r < rows; ++r)
-        for (int v = 0; v < NV; ++v)
-            for (int k = 0; k < 3; ++k) dst[((size_t)r * NVP + v) * 4 + k] = src_rows[(size_t)r * NV3 + 3 * v + k];
-}
-
-template <typename T>
-static int upload_as(T** dst, const std::vector<float>& src) {
-    HIP_TRY(hipMalloc((void**)dst, src.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
-}
-
+// build the tables, upload them, fit the LDS; any failure frees what was allocated and leaves *out alone
 extern "C" int ihmr_mano_create(const ihmr_mano_arrays* h, ihmr_mano** out) {
     if (!h || !out) return -1;
+    ManoTables t;
+    if (build_mano_tables(*h, t)) return -1;
     ihmr_mano* m = new ihmr_mano();
     memset(m, 0, sizeof(*m));
-    std::vector<float> vt(h->v_template, h->v_template + NV3), pd(h->posedirs, h->posedirs + (size_t)NPF * NV3),
-        wts(h->lbs_weights, h->lbs_weights + NV * NJ), jr(h->J_regressor, h->J_regressor + NJ * NV);
-    std::vector<float> sd_t, J_t, J_sd;
-    derive_shape_constants(h->J_regressor, h->v_template, h->shapedirs, sd_t, J_t, J_sd);
-    std::vector<float> pm(48, 0.f);
-    for (int i = 0; i < 45; ++i) pm[3 + i] = h->hands_mean[i];
-    std::vector<int32_t> par(h->parents, h->parents + NJ), depth(NJ, 0), tips(h->tip_ids, h->tip_ids + IHMR_NUM_TIPS);
-    int maxd = 0;
-    for (int j = 1; j < NJ; ++j) {
-        if (par[j] < 0 || par[j] >= j) { delete m; return -1; }
-        depth[j] = depth[par[j]] + 1;
-        if (depth[j] > maxd) maxd = depth[j];
-    }
-    std::vector<int32_t> start(NJ + 1, 0), wv;
-    std::vector<float> ww;
-    for (int j = 0; j < NJ; ++j) {
-        for (int v = 0; v < NV; ++v)
-            if (wts[v * NJ + j] != 0.f) { wv.push_back(v); ww.push_back(wts[v * NJ + j]); }
-        start[j + 1] = (int32_t)wv.size();
-    }
-    // by vertex: the (up to) four non-zero weights in joint order (a zero weight adds an exact zero to the skinning sums, so
-    // leaving the zeros out changes no bit); an asset with a denser vertex keeps the 16-joint loops
-    std::vector<float> w4w((size_t)NV * 4, 0.f);
-    std::vector<uint32_t> w4j(NV, 0u);
-    int sparse4 = 1;
-    for (int v = 0; v < NV; ++v) {
-        int n = 0;
-        for (int j = 0; j < NJ; ++j)
-            if (wts[v * NJ + j] != 0.f) {
-                if (n < 4) { w4w[(size_t)v * 4 + n] = wts[v * NJ + j]; w4j[v] |= (uint32_t)j << (8 * n); }
-                ++n;
-            }
-        if (n > 4) sparse4 = 0;
-    }
-    std::vector<int32_t> seg_q, jseg(NJ + 1, 0);
-    for (int j = 0; j < NJ; ++j) {
-        jseg[j] = (int32_t)seg_q.size();
-        for (int q = start[j]; q < start[j + 1]; q += LBS_SEG) seg_q.push_back(q);
-    }
-    jseg[NJ] = (int32_t)seg_q.size();
-    seg_q.push_back((int32_t)wv.size());
-    // segment s of joint j ends at min(next segment start, end of the joint's list)
-    std::vector<int32_t> fsoa((size_t)3 * NFP, 0);
-    for (int f = 0; f < NFP; ++f)
-        for (int k = 0; k < 3; ++k) {
-            const int32_t id = h->faces[(f < NF ? f : 0) * 3 + k];
-            if (id < 0 || id >= NV) { delete m; return -1; }
-            fsoa[(size_t)k * NFP + f] = id;
-        }
-    std::vector<uint32_t> fpk(NFP, 0u);
-    for (int f = 0; f < NFP; ++f)
-        fpk[f] = (uint32_t)fsoa[f] | ((uint32_t)fsoa[(size_t)NFP + f] << 10) | ((uint32_t)fsoa[(size_t)2 * NFP + f] << 20);
-    std::vector<float> pd4, sd4, vt4;
-    pack4(pd.data(), NPF, pd4);
-    pack4(sd_t.data(), 10, sd4);
-    pack4(vt.data(), 1, vt4);
-    int rc = 0;
-    rc |= upload_as(&m->pd4, pd4); rc |= upload_as(&m->sd4, sd4); rc |= upload_as(&m->vt4, vt4);
-    rc |= upload(&m->v_template, vt); rc |= upload(&m->shapedirs_t, sd_t); rc |= upload(&m->posedirs, pd);
-    rc |= upload(&m->J_template, J_t); rc |= upload(&m->J_shapedirs, J_sd); rc |= upload(&m->weights, wts);
-    rc |= upload_as(&m->w4_w, w4w); rc |= upload(&m->w4_j, w4j);
-    m->sparse4 = sparse4;
-    rc |= upload(&m->pose_mean, pm); rc |= upload(&m->parents, par); rc |= upload(&m->depth, depth);
-    rc |= upload(&m->tip_ids, tips); rc |= upload(&m->wj_start, start); rc |= upload(&m->wj_vert, wv);
-    rc |= upload(&m->wj_w, ww); rc |= upload(&m->seg_q, seg_q); rc |= upload(&m->jseg_start, jseg); rc |= upload(&m->faces, fsoa); rc |= upload(&m->faces_pk, fpk); rc |= upload(&m->J_regressor, jr);
-    m->max_depth = maxd;
-    m->nnz = (int)wv.size();
-    m->nseg = (int)seg_q.size() - 1;
-    if (m->nseg > LBS_SEG_CAP) { ihmr_mano_destroy(m); return -1; }
-    // lbs_bwd1 keeps the per-segment partial sums in dynamic LDS (48 B per segment on top of ~36 KB static): dense
-    // weight matrices (up to ~960 segments) go past the default 64 KB per workgroup, so raise the cap to what is needed --
-    // for every instantiation that is launched with dynamic LDS, and checked: a kernel whose static + dynamic LDS does not fit
-    // the device is never launched (m->tail_fits = 0: ihmr_opt_run_stage falls back to the three separate launches)
-    {
-        const int dyn = m->nseg * 12 * (int)sizeof(float);
-        hipError_t e1 = hipFuncSetAttribute((const void*)lbs_bwd1_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
-        hipError_t e2 = hipFuncSetAttribute((const void*)lbs_bwd1_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
-        if (e1 != hipSuccess || e2 != hipSuccess) { ihmr_mano_destroy(m); return (int)(e1 != hipSuccess ? e1 : e2); }
-        int dev = 0, lds_max = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
-        // (opt_tail_kernel_trans has no dynamic LDS: it is checked like the others and asks for none)
-        const void* tails[4] = {(const void*)opt_tail_kernel<true, true>, (const void*)opt_tail_kernel<true>, (const void*)opt_tail_kernel<false>,
-                                (const void*)opt_tail_kernel_trans};
-        m->tail_fits = 1;
-        const int tail_dyn = opt_tail_dynamic_lds(m->nseg);
-        for (const void* k : tails) {
-            hipFuncAttributes fa;
-            const int dyn_k = k == (const void*)opt_tail_kernel_trans ? 0 : tail_dyn;
-            if (hipFuncGetAttributes(&fa, k) != hipSuccess || (long)fa.sharedSizeBytes + dyn_k > (long)lds_max ||
-                (dyn_k && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, dyn_k) != hipSuccess))
-                m->tail_fits = 0;
-        }
-        (void)hipGetLastError();
-    }
-    if (rc) return rc;
+    m->sparse4 = t.sparse4;
+    m->max_depth = t.max_depth;
+    m->nnz = t.nnz;
+    m->nseg = t.nseg;
+    int rc = mano_buffers(*m, t, [](void** dev, const void* host, size_t bytes) {
+        HIP_TRY(hipMalloc(dev, bytes));
+        HIP_TRY(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
+        return 0;
+    });
+    if (!rc) rc = mano_lds_fit(m);
+    if (rc) { ihmr_mano_destroy(m); return rc; }
     *out = m;
     return 0;
 }
 
 extern "C" int ihmr_mano_destroy(ihmr_mano* m) {
     if (!m) return 0;
-    void* ptrs[] = {m->v_template, m->shapedirs_t, m->posedirs, m->J_template, m->J_shapedirs, m->weights, m->pose_mean,
-                    m->parents, m->depth, m->tip_ids, m->wj_start, m->wj_vert, m->wj_w, m->faces, m->J_regressor, m->pd4, m->sd4, m->vt4, m->seg_q, m->jseg_start,
-                    m->w4_w, m->w4_j, m->faces_pk};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    mano_buffers(*m, ManoTables(), [](void** dev, const void*, size_t) {
+        if (*dev) (void)hipFree(*dev);
+        return 0;
+    });
     delete m;
     return 0;
 }
 
 extern "C" int ihmr_mano_update_shapedirs(ihmr_mano* m, const float* shapedirs_host) {
     if (!m || !shapedirs_host) return -1;
-    std::vector<float> jr((size_t)NJ * NV), vt(NV3), sd_t, J_t, J_sd;
-    HIP_TRY(hipMemcpy(jr.data(), m->J_regressor, jr.size() * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(vt.data(), m->v_template, vt.size() * 4, hipMemcpyDeviceToHost));
-    derive_shape_constants(jr.data(), vt.data(), shapedirs_host, sd_t, J_t, J_sd);
-    HIP_TRY(hipMemcpy(m->shapedirs_t, sd_t.data(), sd_t.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(m->J_shapedirs, J_sd.data(), J_sd.size() * 4, hipMemcpyHostToDevice));
-    std::vector<float> sd4;
-    pack4(sd_t.data(), 10, sd4);
-    HIP_TRY(hipMemcpy(m->sd4, sd4.data(), sd4.size() * 4, hipMemcpyHostToDevice));
+    ManoTables t;
+    t.J_regressor.resize((size_t)NJ * NV);
+    t.v_template.resize(NV3);
+    HIP_TRY(hipMemcpy(t.J_regressor.data(), m->J_regressor, t.J_regressor.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(t.v_template.data(), m->v_template, t.v_template.size() * 4, hipMemcpyDeviceToHost));
+    build_shape_tables(shapedirs_host, t);
+    HIP_TRY(hipMemcpy(m->shapedirs_t, t.shapedirs_t.data(), t.shapedirs_t.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->J_shapedirs, t.J_shapedirs.data(), t.J_shapedirs.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->sd4, t.sd4.data(), t.sd4.size() * 4, hipMemcpyHostToDevice));
     return 0;
 }
 

@@ -29,8 +29,7 @@
 #define LBS_TILE_V 195    // vertices per skin workgroup (4 x 195 = 780 >= 778)
 #define LBS_KG 25         // bwd2: K groups (split-K partial sums, reduced in fixed order by bwd3)
 #define LBS_KC 3          // bwd2: 32-column chunks per K group: 25 x 3 x 32 = 2400 >= 2334 basis columns
-#define LBS_SEG 13         // CSR entries per dA segment
-#define LBS_SEG_CAP 1024   // >= 778*16/13 + 16: every weight matrix fits
+// (LBS_SEG, CSR entries per dA segment, and LBS_SEG_CAP: mano_tables.h, which cuts the segments)
 #define LBS_CSR_CAP 4096   // non-zero skinning weights staged in LDS by bwd1 (MANO-like: <= 4-5 per vertex); else read from L2
 
 // skeleton record (floats), one per hand

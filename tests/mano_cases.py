@@ -147,6 +147,21 @@ def check_outputs(tag, got, f64, o32, rows=None):
 
 
 # ----------------------------------------------------------------------------------- the skin kernel's deal of hands to workgroups
+def dense_weight_asset(arr, nnz=7, seed=5):
+    """The synthetic asset with up to `nnz` non-zero skinning weights per vertex (rows still sum to 1): MANO's own weights have at
+    most four, which is what the kernels' short skinning loops assume -- a denser asset must take their 16-joint form."""
+    rng = np.random.default_rng(seed)
+    a = dict(arr)
+    w = np.array(arr["lbs_weights"], dtype=np.float64)
+    for v in range(0, w.shape[0], 3):
+        extra = rng.choice(w.shape[1], size=nnz, replace=False)
+        w[v, extra] += rng.uniform(0.02, 0.2, size=nnz)
+    w /= w.sum(axis=1, keepdims=True)
+    a["lbs_weights"] = w.astype(arr["lbs_weights"].dtype)
+    assert int((a["lbs_weights"] != 0).sum(axis=1).max()) > 4
+    return a
+
+
 def skin_hands_per_group(N):
     return 4 if N <= SMALL_MAX_HANDS else 8
 

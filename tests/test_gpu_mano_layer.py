@@ -31,9 +31,8 @@ FILL = 0xA5
 
 @pytest.fixture(scope="module")
 def assets(mano_arrays):
-    from test_gpu_parity import _dense_weight_asset
     right, left = mano_arrays
-    return {"right": right, "left": left, "dense": _dense_weight_asset(right)}
+    return {"right": right, "left": left, "dense": MC.dense_weight_asset(right)}
 
 
 @pytest.fixture(scope="module")

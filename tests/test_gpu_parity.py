@@ -89,28 +89,14 @@ def test_lbs_backward_matches_autograd(mano_arrays, which):
             _report(f"lbs d{k} [{which}]", got[k], ref[k], atol=2e-5 * scale)
 
 
-def _dense_weight_asset(arr, nnz=7, seed=5):
-    """The synthetic asset with up to `nnz` non-zero skinning weights per vertex (rows still sum to 1): MANO's own weights have at
-    most four, which is what the kernels' short skinning loops assume -- a denser asset must take their 16-joint form."""
-    rng = np.random.default_rng(seed)
-    a = dict(arr)
-    w = np.array(arr["lbs_weights"], dtype=np.float64)
-    for v in range(0, w.shape[0], 3):
-        extra = rng.choice(w.shape[1], size=nnz, replace=False)
-        w[v, extra] += rng.uniform(0.02, 0.2, size=nnz)
-    w /= w.sum(axis=1, keepdims=True)
-    a["lbs_weights"] = w.astype(arr["lbs_weights"].dtype)
-    assert int((a["lbs_weights"] != 0).sum(axis=1).max()) > 4
-    return a
-
-
 def test_lbs_dense_weight_asset_matches_oracle(mano_arrays):
     """Forward and all gradients of the LBS kernels on an asset whose vertices have MORE than four non-zero skinning weights (the
     16-joint loops) against the oracle; the same inputs on the 4-sparse asset go through the short loops (tests above)."""
     from ihmr_amd import mano
+    from mano_cases import dense_weight_asset
     from oracle.mano_ref import ManoRef
     right, _ = mano_arrays
-    arr = _dense_weight_asset(right)
+    arr = dense_weight_asset(right)
     N = 5
     orient, pose, betas = _rand_mano_inputs(N, 11)
     g = torch.Generator().manual_seed(12)

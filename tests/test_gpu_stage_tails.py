@@ -158,11 +158,11 @@ LDS_PER_WORKGROUP = 163840  # a workgroup's limit on gfx950: the fused tail is t
 
 
 def _dense_weights(arrays):
-    """The lbs_weights of test_gpu_parity._dense_weight_asset, checked on the host: some vertex has more than four non-zero weights (the
+    """The lbs_weights of mano_cases.dense_weight_asset, checked on the host: some vertex has more than four non-zero weights (the
     kernels take their 16-joint loops) and the fused tail still fits -- 2 x 48 B of dynamic LDS per single-joint segment of <= 13 entries
-    (csrc/mano_lbs.h: LBS_SEG); otherwise the fused runs and the separate launches would be the same launches."""
-    from test_gpu_parity import _dense_weight_asset
-    w = _dense_weight_asset(arrays)["lbs_weights"]
+    (csrc/mano_tables.h: LBS_SEG); otherwise the fused runs and the separate launches would be the same launches."""
+    from mano_cases import dense_weight_asset
+    w = dense_weight_asset(arrays)["lbs_weights"]
     assert int((w != 0).sum(axis=1).max()) > 4
     nseg = int(sum(-(-int(n) // 13) for n in (w != 0).sum(axis=0)))
     assert TAIL_STATIC_LDS + 2 * 48 * nseg <= LDS_PER_WORKGROUP, nseg
