@@ -14,6 +14,10 @@
 // grid = B, block = 64: lane j < 42 owns joint j.  out (B,6) doubles:
 //   [0] sum of per-joint errors, [1] number of them, [2] sum of aligned ("inter") errors, [3] number of them,
 //   [4] mean penetration depth [mm], [5] max penetration depth [mm]  ([4],[5] = 0 and not counted unless interacting)
+// The rules are the reference's, literally (statement and case classes: tests/metric_cases.py): a joint counts when its weight is > 0,
+// a hand when its root does; the aligned error is left out when the SUM of the 42 weights is < 2.0, else [3] = the number of w > 0
+// joints and [2] is NaN where the reference divides 0 / 0 (one joint, or no spread of the prediction on an axis); a NaN depth makes
+// both [4] and [5] NaN.  Float32 arithmetic, sums in butterfly order: a sample's six words do not depend on its place in the batch.
 __global__ __launch_bounds__(64) void eval_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
                                                           const float* __restrict__ coll, const float* __restrict__ scale,
                                                           const unsigned char* __restrict__ interacting, int B,
@@ -51,10 +55,14 @@ __global__ __launch_bounds__(64) void eval_metrics_kernel(const float* __restric
     const double err_sum = (double)wave_reduce_sum(err), err_n = (double)wave_reduce_sum(cnt);
 
     // ---- aligned error over all valid joints (metric_utils.py:107-143, no rotation): p' = (p - mean p) / std p * std g + mean g
+    // The sample is left out when the SUM of its 42 weights is < 2.0 (metric_utils.py:131; EVP_MIN_WEIGHT_SUM), not by the number n of
+    // its w > 0 joints.  A kept set without spread on an axis (n = 1; equal predicted coordinates) divides 0 / 0 like the reference:
+    // every joint of the set gets NaN and the set still counts.
     const bool valid = act && w > 0.f;
     const float n = wave_reduce_sum(valid ? 1.f : 0.f);
+    const bool kept = wave_reduce_sum(act ? w : 0.f) >= (float)EVP_MIN_WEIGHT_SUM;     // uniform over the wave; implies n >= 1
     float ierr = 0.f;
-    if (n >= 2.f) {
+    if (kept) {
         float d[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -70,22 +78,24 @@ __global__ __launch_bounds__(64) void eval_metrics_kernel(const float* __restric
     // ---- penetration depth statistics of the 1556 per-vertex values [mm]
     double csum = 0.0;
     float cmax = -INFINITY;
+    bool cnan = false;          // fmaxf drops a NaN, np.max (evaluator.py:173) returns it: a NaN depth makes the maximum NaN
     const bool inter = interacting ? interacting[b] != 0 : true;
     if (inter) {
         for (int v = j; v < 2 * NV; v += 64) {
             const float x = coll[(size_t)b * 2 * NV + v];
             csum += (double)x;
             cmax = fmaxf(cmax, x);
+            cnan |= x != x;
         }
     }
     double cs = csum;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) cs += __shfl_xor(cs, o);
-    const float cm = wave_reduce_max(cmax);
+    const float cm = __ballot(cnan) != 0ull ? NAN : wave_reduce_max(cmax);
     if (j == 0) {
         double* o = out + (size_t)b * 6;
         o[0] = err_sum; o[1] = err_n;
-        o[2] = n >= 2.f ? ierr_sum : 0.0; o[3] = n >= 2.f ? (double)n : 0.0;
+        o[2] = kept ? ierr_sum : 0.0; o[3] = kept ? (double)n : 0.0;
         o[4] = inter ? cs / (double)(2 * NV) * 1000.0 : 0.0;
         o[5] = inter ? (double)cm * 1000.0 : 0.0;
     }

@@ -395,8 +395,8 @@ class Evaluator:
                                               None if it is None else it.data_ptr(), B, out.data_ptr(), hip.stream_ptr()), "ihmr_eval_metrics")
         n_inter = torch.ones(B, device=dev, dtype=torch.float64) if it is None else it.to(torch.float64)
         part = torch.cat([out, n_inter[:, None]], dim=1)      # [.., n_interacting]
-        if keep is not None:
-            part = part * keep.to(dev, torch.float64)[:, None]
+        if keep is not None:      # a selection, not a product: a masked-out row may hold NaN / Inf, and 0 * NaN is NaN
+            part = torch.where(keep.to(dev, torch.bool)[:, None], part, torch.zeros_like(part))
         self._device_parts.append(part)
 
     def update_device_verts(self, pred_right, pred_left, gt_right, gt_left, mano_params_weight, keep=None, scale=None):
@@ -418,8 +418,8 @@ class Evaluator:
                                             w.data_ptr(), None if sc is None else sc.data_ptr(), B, out.data_ptr(), hip.stream_ptr()),
                   "ihmr_eval_mpvpe")
         out = out[:, 0:2] + out[:, 2:4]
-        if keep is not None:
-            out = out * keep.to(dev, torch.float64)[:, None]
+        if keep is not None:      # a selection, as in update_device
+            out = torch.where(keep.to(dev, torch.bool)[:, None], out, torch.zeros_like(out))
         self._device_vert_parts.append(out)
 
     def gather_pred(self, pred_results):
