@@ -1082,10 +1082,11 @@ extern "C" size_t ihmr_render_workspace_bytes(int B, int n_verts) {
     return B > 0 && n_verts > 0 ? sizeof(rnd_vertex) * (size_t)B * (size_t)n_verts : 0;
 }
 
-extern "C" int ihmr_render_meshes(const float* verts, const int32_t* faces, const int32_t* csr_offsets, const int32_t* csr_ids, int n_verts,
-                                  int n_faces, int face_split, const uint8_t* present, const float* albedo, const float* cam,
-                                  const ihmr_render_lights* lights, const uint8_t* background, int S, uint8_t* out_img,
-                                  int32_t* out_face_ids, void* workspace, int B, void* stream) {
+// both forms of the render: `albedo` per hand (B,2,3) or per vertex (B,n_verts,3)
+static int render_launch(bool per_vertex, const float* verts, const int32_t* faces, const int32_t* csr_offsets, const int32_t* csr_ids,
+                         int n_verts, int n_faces, int face_split, const uint8_t* present, const float* albedo, const float* cam,
+                         const ihmr_render_lights* lights, const uint8_t* background, int S, uint8_t* out_img, int32_t* out_face_ids,
+                         void* workspace, int B, void* stream) {
     if (!verts || !faces || !csr_offsets || !csr_ids || !albedo || !cam || !lights || !out_img || !workspace) return -1;
     if (B <= 0 || B > 65535 || n_verts <= 0 || n_faces <= 0 || n_faces > (1 << 24) || n_verts > (1 << 24) || face_split < 0 ||
         face_split > n_faces || S < 16 || S > 2048)
@@ -1093,13 +1094,58 @@ extern "C" int ihmr_render_meshes(const float* verts, const int32_t* faces, cons
     if ((uintptr_t)workspace & 3u) return -1;
     const hipStream_t st = (hipStream_t)stream;
     rnd_vertex* ws = static_cast<rnd_vertex*>(workspace);
-    hipLaunchKernelGGL(render_vertex_kernel, dim3((n_verts + RND_THREADS - 1) / RND_THREADS, B), dim3(RND_THREADS), 0, st, verts, faces,
-                       csr_offsets, csr_ids, n_verts, n_faces, face_split, albedo, cam, *lights, S, ws);
+    const dim3 vgrid((n_verts + RND_THREADS - 1) / RND_THREADS, B);
+    if (per_vertex)
+        hipLaunchKernelGGL(paint_vertex_kernel, vgrid, dim3(RND_THREADS), 0, st, verts, faces, csr_offsets, csr_ids, n_verts, n_faces,
+                           face_split, albedo, cam, *lights, S, ws);
+    else
+        hipLaunchKernelGGL(render_vertex_kernel, vgrid, dim3(RND_THREADS), 0, st, verts, faces, csr_offsets, csr_ids, n_verts, n_faces,
+                           face_split, albedo, cam, *lights, S, ws);
     const int tiles = (S + RND_TILE - 1) / RND_TILE;
     // whole 12-byte runs as three dwords when every run is complete and aligned
     const int vec = S % RND_PPT == 0 && !((uintptr_t)out_img & 3u) && !((uintptr_t)background & 3u);
     hipLaunchKernelGGL(render_raster_kernel, dim3(tiles * tiles, B), dim3(RND_THREADS), 0, st, ws, faces, n_verts, n_faces, face_split,
                        present, background, S, vec, out_img, out_face_ids);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ihmr_render_meshes(const float* verts, const int32_t* faces, const int32_t* csr_offsets, const int32_t* csr_ids, int n_verts,
+                                  int n_faces, int face_split, const uint8_t* present, const float* albedo, const float* cam,
+                                  const ihmr_render_lights* lights, const uint8_t* background, int S, uint8_t* out_img,
+                                  int32_t* out_face_ids, void* workspace, int B, void* stream) {
+    return render_launch(false, verts, faces, csr_offsets, csr_ids, n_verts, n_faces, face_split, present, albedo, cam, lights, background, S,
+                         out_img, out_face_ids, workspace, B, stream);
+}
+
+extern "C" int ihmr_paint_meshes(const float* verts, const int32_t* faces, const int32_t* csr_offsets, const int32_t* csr_ids, int n_verts,
+                                 int n_faces, int face_split, const uint8_t* present, const float* vertex_albedo, const float* cam,
+                                 const ihmr_render_lights* lights, const uint8_t* background, int S, uint8_t* out_img,
+                                 int32_t* out_face_ids, void* workspace, int B, void* stream) {
+    return render_launch(true, verts, faces, csr_offsets, csr_ids, n_verts, n_faces, face_split, present, vertex_albedo, cam, lights,
+                         background, S, out_img, out_face_ids, workspace, B, stream);
+}
+
+extern "C" int ihmr_view_vertices(const float* verts, const uint8_t* present, int n_verts, int n_split, const float* rot, int rot_per_sample,
+                                  const float* pivot, float* out, int B, void* stream) {
+    if (!verts || !rot || !out) return -1;
+    if (B <= 0 || B > 65535 || n_verts <= 0 || n_verts > (1 << 24) || n_split < 0 || n_split > n_verts || (rot_per_sample != 0 && rot_per_sample != 1))
+        return -1;
+    const uintptr_t bytes = (uintptr_t)B * (uintptr_t)n_verts * 12u, a = (uintptr_t)verts, o = (uintptr_t)out;
+    if (a < o + bytes && o < a + bytes) return -1;                              // in place or overlapping: a vertex would be read after it was written
+    hipLaunchKernelGGL(view_vertices_kernel, dim3(B), dim3(RND_THREADS), 0, (hipStream_t)stream, verts, present, n_verts, n_split, rot,
+                       rot_per_sample, pivot, out);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ihmr_heat_colours(const float* depth, const float* albedo, const float* hot, float lo, float hi, int n_verts, int n_split,
+                                 int layout, float* out, int B, void* stream) {
+    if (!depth || !albedo || !hot || !out) return -1;
+    if (B <= 0 || B > 65535 || n_verts <= 0 || n_verts > (1 << 24) || n_split < 0 || n_split > n_verts) return -1;
+    if (!rnd_finite(lo) || !rnd_finite(hi) || !(hi > lo)) return -1;
+    if (layout != 0 && layout != 1) return -1;
+    if (layout == 1 && n_verts != 2 * n_split) return -1;
+    hipLaunchKernelGGL(heat_colours_kernel, dim3((n_verts + RND_THREADS - 1) / RND_THREADS, B), dim3(RND_THREADS), 0, (hipStream_t)stream,
+                       depth, albedo, hot[0], hot[1], hot[2], lo, hi, n_verts, n_split, layout, out);
     return (int)hipGetLastError();
 }
 

@@ -9,6 +9,10 @@
 //                          -- a chunk can never overflow it --, then every thread walks the list with broadcast LDS reads.  Depth, face
 //                          id and the interpolation weights of the visible face stay in registers: the z-buffer never touches memory.
 //                          Colours are fetched once per pixel, for the visible face only.  One 12-byte run of output per thread.
+//   paint_vertex_kernel    render_vertex_kernel with one albedo per vertex (ihmr_paint_meshes); both call render_vertex_body
+//   view_vertices_kernel   one workgroup per sample: the default pivot (an exact min / max reduction by wave shuffles and LDS), then
+//                          q = (p - c) R + c for every vertex (ihmr_view_vertices)
+//   heat_colours_kernel    grid (vertex blocks, B): per-vertex albedo from a depth table (ihmr_heat_colours)
 //   draw_keypoints_kernel  one workgroup of one wave per sample: the keypoints in order, one lane per cell of the 7 x 7 box, so that a
 //                          later disc overwrites an earlier one.
 // No float atomics, no hand-offs between workgroups, no scratch (tests/test_render_cpu.py reads the code-object metadata).
@@ -22,11 +26,13 @@
 #define RND_PPT 4                      /* pixels per thread: one 12-byte run */
 #define RND_KP_THREADS 64
 
-__global__ __launch_bounds__(RND_THREADS) void render_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces,
-                                                                    const int32_t* __restrict__ csr_off, const int32_t* __restrict__ csr_ids,
-                                                                    int nV, int nF, int split, const float* __restrict__ albedo,
-                                                                    const float* __restrict__ cam, ihmr_render_lights L, int S,
-                                                                    rnd_vertex* __restrict__ ws) {
+// the vertex stage of both vertex kernels: PER_VERTEX reads the albedo of vertex v from a (B,nV,3) table, otherwise from the (B,2,3)
+// table of the vertex's hand (the hand of its first incident face)
+template <bool PER_VERTEX>
+__device__ __forceinline__ void render_vertex_body(const float* __restrict__ verts, const int32_t* __restrict__ faces,
+                                                   const int32_t* __restrict__ csr_off, const int32_t* __restrict__ csr_ids, int nV, int nF,
+                                                   int split, const float* __restrict__ albedo, const float* __restrict__ cam,
+                                                   const ihmr_render_lights& L, int S, rnd_vertex* __restrict__ ws) {
     const int v = blockIdx.x * RND_THREADS + threadIdx.x, b = blockIdx.y;
     if (v >= nV) return;
     rnd_vertex out;
@@ -54,12 +60,94 @@ __global__ __launch_bounds__(RND_THREADS) void render_vertex_kernel(const float*
         const float p0[3] = {vb[3 * v], vb[3 * v + 1], vb[3 * v + 2]};
         float p[3];
         rnd_translate(p0, cm, p);
-        const float* al = albedo + ((size_t)b * 2 + hand) * 3;
+        const float* al = albedo + (PER_VERTEX ? (size_t)b * nV + v : (size_t)b * 2 + hand) * 3;
         const float alb[3] = {al[0], al[1], al[2]};
         rnd_shade(n, p, alb, &L, out.c);
         rnd_project(p, S, &out);
     }
     ws[(size_t)b * nV + v] = out;
+}
+
+__global__ __launch_bounds__(RND_THREADS) void render_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces,
+                                                                    const int32_t* __restrict__ csr_off, const int32_t* __restrict__ csr_ids,
+                                                                    int nV, int nF, int split, const float* __restrict__ albedo,
+                                                                    const float* __restrict__ cam, ihmr_render_lights L, int S,
+                                                                    rnd_vertex* __restrict__ ws) {
+    render_vertex_body<false>(verts, faces, csr_off, csr_ids, nV, nF, split, albedo, cam, L, S, ws);
+}
+
+__global__ __launch_bounds__(RND_THREADS) void paint_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces,
+                                                                   const int32_t* __restrict__ csr_off, const int32_t* __restrict__ csr_ids,
+                                                                   int nV, int nF, int split, const float* __restrict__ albedo,
+                                                                   const float* __restrict__ cam, ihmr_render_lights L, int S,
+                                                                   rnd_vertex* __restrict__ ws) {
+    render_vertex_body<true>(verts, faces, csr_off, csr_ids, nV, nF, split, albedo, cam, L, S, ws);
+}
+
+// One workgroup per sample.  Without a pivot: every thread takes its vertices of the drawn hands into a bounding box, the boxes are
+// merged across the wave by shuffles and across the four waves through LDS (rnd_min / rnd_max are order independent, so every thread
+// ends with the same box whatever the arrangement).  Then every vertex of the sample is transformed, drawn or not.
+__global__ __launch_bounds__(RND_THREADS) void view_vertices_kernel(const float* __restrict__ verts, const uint8_t* __restrict__ present,
+                                                                    int nV, int split, const float* __restrict__ rot, int rot_per_sample,
+                                                                    const float* __restrict__ pivot, float* __restrict__ out) {
+    __shared__ float box[RND_THREADS / 64][6];
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const float* vb = verts + (size_t)b * nV * 3;
+    float c[3];
+    if (pivot) {
+        c[0] = pivot[3 * b]; c[1] = pivot[3 * b + 1]; c[2] = pivot[3 * b + 2];
+    } else {
+        const int draw0 = present ? present[2 * b] : 1, draw1 = present ? present[2 * b + 1] : 1;
+        float mn[3], mx[3];
+        rnd_bbox_empty(mn, mx);
+        for (int v = t; v < nV; v += RND_THREADS) {
+            if (!(v < split ? draw0 : draw1)) continue;
+            const float p[3] = {vb[3 * v], vb[3 * v + 1], vb[3 * v + 2]};
+            rnd_bbox_take(p, mn, mx);
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            float mn2[3], mx2[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { mn2[a] = __shfl_xor(mn[a], m, 64); mx2[a] = __shfl_xor(mx[a], m, 64); }
+            rnd_bbox_merge(mn2, mx2, mn, mx);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { box[wave][a] = mn[a]; box[wave][3 + a] = mx[a]; }
+        }
+        __syncthreads();
+        rnd_bbox_empty(mn, mx);
+#pragma unroll
+        for (int w = 0; w < RND_THREADS / 64; ++w) rnd_bbox_merge(&box[w][0], &box[w][3], mn, mx);
+        rnd_bbox_centre(mn, mx, c);
+    }
+    const float* rb = rot + (rot_per_sample ? (size_t)b * 9 : 0);
+    float R[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = rb[k];
+    float* ob = out + (size_t)b * nV * 3;
+    for (int v = t; v < nV; v += RND_THREADS) {
+        const float p[3] = {vb[3 * v], vb[3 * v + 1], vb[3 * v + 2]};
+        float q[3];
+        rnd_view_point(p, c, R, q);
+        ob[3 * v] = q[0]; ob[3 * v + 1] = q[1]; ob[3 * v + 2] = q[2];
+    }
+}
+
+// grid (vertex blocks, B): the colour of one vertex from the depth entry its layout names and its hand's base colour
+__global__ __launch_bounds__(RND_THREADS) void heat_colours_kernel(const float* __restrict__ depth, const float* __restrict__ albedo,
+                                                                   float hot0, float hot1, float hot2, float lo, float hi, int nV, int split,
+                                                                   int layout, float* __restrict__ out) {
+    const int v = blockIdx.x * RND_THREADS + threadIdx.x, b = blockIdx.y;
+    if (v >= nV) return;
+    const float d = depth[(size_t)b * nV + rnd_heat_entry(v, split, layout)];
+    const float* al = albedo + ((size_t)b * 2 + (v >= split)) * 3;
+    const float base[3] = {al[0], al[1], al[2]}, hot[3] = {hot0, hot1, hot2};
+    float c[3];
+    rnd_heat_colour(d, lo, hi, base, hot, c);
+    float* o = out + ((size_t)b * nV + v) * 3;
+    o[0] = c[0]; o[1] = c[1]; o[2] = c[2];
 }
 
 __global__ __launch_bounds__(RND_THREADS) void render_raster_kernel(const rnd_vertex* __restrict__ ws, const int32_t* __restrict__ faces,

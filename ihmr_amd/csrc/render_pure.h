@@ -20,6 +20,15 @@
 //   depth      l_i = (float)E_i / (float)|2A|;  w = (l0*iz0 + l1*iz1) + l2*iz2;  the visible face has the largest w, ties to the lowest index
 //   colour     c[ch] = (((l0*iz0)*c0[ch] + (l1*iz1)*c1[ch]) + (l2*iz2)*c2[ch]) / w;  byte = min((int)(c * 255), 255)
 //   keypoints  centre = (int)(((k + 1) * 0.5) * S) per axis (truncation); filled disc of half-widths 3, 3, 2, 1 on rows |dy| = 0..3
+// Rotated views and the penetration heat map (ihmr_view_vertices / ihmr_heat_colours; tests/render_views_ref.py restates them):
+//   view       d = p - c;  q[j] = ((d0*R[0][j] + d1*R[1][j]) + d2*R[2][j]) + c[j]: the row vector (p - c) times R, plus c, as
+//              np.dot(verts - center, around) + center of SMPLRenderer.rotated (utils/vis_util.py:177-178).  (p - c) + c rounds, so the
+//              identity matrix does not give p back: "no view" skips the transform, it is never an identity rotation
+//   pivot      c = 0.5 * (mn + mx) per axis, mn / mx over the vertices of the hands that are drawn (vertex v belongs to hand 0 iff
+//              v < n_split) whose three coordinates are all finite; c = 0 when there is none.  min and max order -0 below +0, so the
+//              result is one float however the reduction is arranged (the reference takes verts.mean(axis=0): DESIGN.md section 8.1)
+//   heat       t = (d - lo) / (hi - lo);  t = !(t > 0) ? 0 : (t > 1 ? 1 : t) (a NaN depth gives the base colour);
+//              out[ch] = base[ch] + t * (hot[ch] - base[ch]);  under layout 1 vertex v reads the depth entry of rnd_heat_entry
 // Nothing here touches memory other than its arguments.
 #pragma once
 #include <math.h>
@@ -152,3 +161,49 @@ RND_PURE int rnd_colour_byte(const float* q, float w, float c0, float c1, float 
 RND_PURE int rnd_kp_ok(float k) { return fabsf(k) < 1.0e6f; }                       // false for NaN / infinities: (int) would be undefined
 RND_PURE int rnd_kp_centre(float k, int S) { return (int)(((k + 1.0f) * 0.5f) * (float)S); }
 RND_PURE int rnd_disc_half_width(int ady) { return ady <= 1 ? 3 : (ady == 2 ? 2 : (ady == 3 ? 1 : -1)); }
+
+// ------------------------------------------------------------------------------------------ rotated views, penetration heat map
+RND_PURE int rnd_finite(float x) { return fabsf(x) <= 3.4028234663852886e38f; }              // false for NaN and the infinities
+// minimum / maximum of two numbers (never NaN here) under the order that puts -0 below +0: commutative and associative
+RND_PURE float rnd_min(float a, float b) { return (b < a || (b == a && __builtin_signbit(b))) ? b : a; }
+RND_PURE float rnd_max(float a, float b) { return (b > a || (b == a && !__builtin_signbit(b))) ? b : a; }
+
+// q = (p - c) R + c, R row major (R[3 * i + j])
+RND_PURE void rnd_view_point(const float* p, const float* c, const float* R, float* q) {
+    const float d0 = p[0] - c[0], d1 = p[1] - c[1], d2 = p[2] - c[2];
+    for (int j = 0; j < 3; ++j) q[j] = ((d0 * R[j] + d1 * R[3 + j]) + d2 * R[6 + j]) + c[j];
+}
+
+// the bounding box of the default pivot: empty (mn > mx), one more vertex, two boxes merged, and the pivot of a box
+RND_PURE void rnd_bbox_empty(float* mn, float* mx) {
+    for (int a = 0; a < 3; ++a) { mn[a] = INFINITY; mx[a] = -INFINITY; }
+}
+RND_PURE void rnd_bbox_take(const float* p, float* mn, float* mx) {
+    if (!(rnd_finite(p[0]) && rnd_finite(p[1]) && rnd_finite(p[2]))) return;
+    for (int a = 0; a < 3; ++a) { mn[a] = rnd_min(mn[a], p[a]); mx[a] = rnd_max(mx[a], p[a]); }
+}
+RND_PURE void rnd_bbox_merge(const float* mn2, const float* mx2, float* mn, float* mx) {
+    for (int a = 0; a < 3; ++a) { mn[a] = rnd_min(mn[a], mn2[a]); mx[a] = rnd_max(mx[a], mx2[a]); }
+}
+RND_PURE void rnd_bbox_centre(const float* mn, const float* mx, float* c) {
+    const int any = mn[0] <= mx[0];                                                          // a box that took a vertex has mn <= mx on every axis
+    for (int a = 0; a < 3; ++a) c[a] = any ? 0.5f * (mn[a] + mx[a]) : 0.0f;
+}
+// the default pivot of one sample: verts (n_verts,3), draw0 / draw1 say which hands are drawn
+RND_PURE void rnd_bbox_mid(const float* verts, int n_verts, int n_split, int draw0, int draw1, float* c) {
+    float mn[3], mx[3];
+    rnd_bbox_empty(mn, mx);
+    for (int v = 0; v < n_verts; ++v)
+        if (v < n_split ? draw0 : draw1) rnd_bbox_take(verts + 3 * (size_t)v, mn, mx);
+    rnd_bbox_centre(mn, mx, c);
+}
+
+// the depth entry vertex v reads: layout 0 its own; layout 1 the collision module's order (entry h * n_split + k was sampled at vertex
+// k of hand 1 - h: include/ihmr_hip.h, ihmr_sdf_collision), which needs n_verts == 2 * n_split
+RND_PURE int rnd_heat_entry(int v, int n_split, int layout) { return layout ? (v < n_split ? n_split + v : v - n_split) : v; }
+
+RND_PURE void rnd_heat_colour(float d, float lo, float hi, const float* base, const float* hot, float* out) {
+    float t = (d - lo) / (hi - lo);
+    t = !(t > 0.0f) ? 0.0f : (t > 1.0f ? 1.0f : t);
+    for (int ch = 0; ch < 3; ++ch) out[ch] = base[ch] + t * (hot[ch] - base[ch]);
+}

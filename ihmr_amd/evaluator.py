@@ -719,14 +719,22 @@ class Evaluator:
             pred["img_name"] = osp.join(*(record[-4:-2] + ["_".join(record[-2:])]))
             os.makedirs(osp.dirname(osp.join(res_dir, pred["img_name"])) or ".", exist_ok=True)
 
-    def visualize_result(self, res_vis_dir, res_obj_dir, size_type="double", batch_size=64, image_loader=None):
+    def visualize_result(self, res_vis_dir, res_obj_dir, size_type="double", batch_size=64, image_loader=None, views=(),
+                         collision_map=False, collision_range=(0.0, 0.005)):
         """evaluator.py:231-275 for every stored record: the image padded and resized to ``final_size`` (``size_type`` 'double' =
         2 x inputSize, 'normalized' = inputSize, 'origin' = the image's longer side, which the resize kernel needs to be a multiple
         of 4), both hands rendered over it for an interacting sample (right ``light_green``, left ``light_blue``) and the one hand of
         ``hand_type`` otherwise, image stacked over render and written to ``<res_vis_dir>/<img_name>`` as .jpg, the mesh to
         ``<res_obj_dir>/<img_name>.obj``.  ``image_loader(path) -> (H,W,3) uint8 BGR`` replaces the PIL loader.  The reference forks
         16 processes of OpenDR; here the records go through the device in batches of ``batch_size``: one resize launch and one render
-        per batch and image size."""
+        per batch and image size.
+
+        ``views``: ``(axis, deg)`` pairs or (3,3) matrices; one more panel per view, the hands turned about the middle of their
+        bounding box and drawn on white (``MeshRenderer.render_views``), is stacked under image and render.  ``collision_map``:
+        the hands of an interacting sample are painted from the record's ``collision_loss_origin_scale`` (``render.penetration_colors``:
+        the hand's colour at ``collision_range[0]`` metres of penetration or less, red from ``collision_range[1]`` on), in the
+        camera's view and in every other; a flipped record's table was swapped back with its hands (``_flip_back_data``).  With
+        the defaults the files are what they are without these arguments."""
         import torch
 
         from . import hip, render, ry_utils
@@ -742,6 +750,7 @@ class Evaluator:
         renderer = render.MeshRenderer(faces["right"], faces["left"], nv, nv)
         two = np.array([render.COLORS["light_green"], render.COLORS["light_blue"]], np.float32)
         one = np.array([render.SINGLE_HAND_COLOR, render.SINGLE_HAND_COLOR], np.float32)
+        views = list(views)
         for start in range(0, len(self.pred_results), batch_size):
             chunk = self.pred_results[start:start + batch_size]
             images = [loader(r["img_path"]) for r in chunk]
@@ -756,9 +765,19 @@ class Evaluator:
                 present = np.array([[1, 1] if it else [r["hand_type"] == "right", r["hand_type"] == "left"] for r, it in zip(recs, inter)], np.uint8)
                 colors = np.stack([two if it else one for it in inter])
                 up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-                out = renderer.render(up(np.stack([hand(r, "right") for r in recs])), up(np.stack([hand(r, "left") for r in recs])),
-                                      up(np.stack([np.asarray(r["pred_cam_params"], np.float32)[:3] for r in recs])), img,
-                                      present=up(present), colors=up(colors))
+                scene = (up(np.stack([hand(r, "right") for r in recs])), up(np.stack([hand(r, "left") for r in recs])),
+                         up(np.stack([np.asarray(r["pred_cam_params"], np.float32)[:3] for r in recs])))
+                if not views and not collision_map:
+                    out = renderer.render(*scene, img, present=up(present), colors=up(colors))
+                else:
+                    paint = None
+                    if collision_map:
+                        no_depth = np.zeros(2 * nv, np.float32)            # a depth of zero is the hand's own colour
+                        depth = np.stack([np.asarray(r["collision_loss_origin_scale"], np.float32).reshape(2 * nv) if it else no_depth
+                                          for r, it in zip(recs, inter)])
+                        paint = render.penetration_colors(up(depth), up(colors), lo=collision_range[0], hi=collision_range[1])
+                    panels = renderer.render_views(*scene, [None] + views, img, present=up(present), colors=up(colors), vertex_colors=paint)
+                    out = panels.reshape(len(recs), (1 + len(views)) * S, S, 3)    # the camera's view, then one panel per view
                 res = torch.cat([img, out], dim=1).cpu().numpy()               # image over render (evaluator.py:250)
                 for k, r in enumerate(recs):
                     if inter[k]:                                               # evaluator.py:206-221
@@ -770,12 +789,33 @@ class Evaluator:
                     ry_utils.save_mesh_to_obj(osp.join(res_obj_dir, r["img_name"])[:-4] + ".obj", verts, f)
 
 
+def parse_views(text):
+    """``"y:90,x:-90"`` -> ``[("y", 90.0), ("x", -90.0)]`` (the ``--views`` option)."""
+    out = []
+    for item in filter(None, (t.strip() for t in text.split(","))):
+        axis, sep, deg = item.partition(":")
+        if not sep or axis not in ("x", "y", "z"):
+            raise ValueError(f"a view is axis:degrees with axis x, y or z, not {item!r}")
+        out.append((axis, float(deg)))
+    return out
+
+
 def main():
-    """evaluator.py:278-291: ``python -m ihmr_amd.evaluator METHOD DATASET`` visualises ``evaluate_results/METHOD/DATASET.pkl``."""
+    """evaluator.py:278-291: ``python -m ihmr_amd.evaluator METHOD DATASET [--views y:90,x:-90] [--collision_map]`` visualises
+    ``evaluate_results/METHOD/DATASET.pkl``; ``--views`` adds one panel per ``axis:degrees`` entry, ``--collision_map`` paints the
+    interacting hands by their per-vertex penetration depth."""
+    import argparse
     import shutil
 
     from . import ry_utils
-    method, dataset = sys.argv[1], sys.argv[2]
+    ap = argparse.ArgumentParser(prog="python -m ihmr_amd.evaluator")
+    ap.add_argument("method")
+    ap.add_argument("dataset")
+    ap.add_argument("--views", default="", help="comma-separated axis:degrees entries, e.g. y:90,x:-90")
+    ap.add_argument("--collision_map", action="store_true")
+    args = ap.parse_args()
+    method, dataset = args.method, args.dataset
+    views = parse_views(args.views)
     pkl_path = osp.join("evaluate_results", method, f"{dataset}.pkl")
     assert osp.exists(pkl_path)
     evaluator = ry_utils.load_pkl(pkl_path)
@@ -785,7 +825,7 @@ def main():
         if osp.isdir(d):
             shutil.rmtree(d)
         os.makedirs(d)
-    evaluator.visualize_result(res_vis_dir, res_obj_dir)
+    evaluator.visualize_result(res_vis_dir, res_obj_dir, views=views, collision_map=args.collision_map)
 
 
 if __name__ == "__main__":

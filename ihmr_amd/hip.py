@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = [
     "ihmr_debug_force_lbs_bwd2_streaming", "ihmr_debug_force_full_skin", "ihmr_debug_force_generic_tail", "ihmr_version", "ihmr_copy_segments", "ihmr_root_align_joints",
     "ihmr_augment_images", "ihmr_augment_labels",
     "ihmr_render_workspace_bytes", "ihmr_render_meshes", "ihmr_draw_keypoints",
+    "ihmr_view_vertices", "ihmr_heat_colours", "ihmr_paint_meshes",
     "ihmr_conv_igemm_bf16", "ihmr_pack_image_bf16", "ihmr_maxpool3x3s2_bf16", "ihmr_avgpool_relu_bf16", "ihmr_cast_f32_bf16",
 ]
 
@@ -319,6 +320,12 @@ def lib():
         L.ihmr_render_workspace_bytes.restype = C.c_size_t
         L.ihmr_render_meshes.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp, C.POINTER(RenderLights), vp, i, vp, vp, vp, i, vp]
         L.ihmr_draw_keypoints.argtypes = [vp, vp, vp, C.c_char_p, i, i, i, vp]
+        # (an older library named with IHMR_HIP_LIBRARY lacks these three: a call of them raises AttributeError)
+        for name, sig in (("ihmr_view_vertices", [vp, vp, i, i, vp, i, vp, vp, i, vp]),
+                          ("ihmr_heat_colours", [vp, vp, C.POINTER(f * 3), f, f, i, i, i, vp, i, vp]),
+                          ("ihmr_paint_meshes", [vp, vp, vp, vp, i, i, i, vp, vp, vp, C.POINTER(RenderLights), vp, i, vp, vp, vp, i, vp])):
+            if hasattr(L, name):
+                getattr(L, name).argtypes = sig
         L.ihmr_opt_sdf_stats.argtypes = [vp, vp, C.POINTER(OptIO), i, C.POINTER(OptWeights), vp, vp]
         L.ihmr_opt_sdf_counters.argtypes = [C.POINTER(OptIO), i, vp, i]
         L.ihmr_opt_sdf_inside_bits.argtypes = [C.POINTER(OptIO), i, vp, vp]

@@ -10,6 +10,11 @@ background -- is :func:`scene_setup` / :func:`scene_together` / :func:`scene_sin
 pixel arithmetic (``csrc/render_pure.h``) is this build's own: PARITY UNPINNED against OpenDR; no silhouette
 anti-aliasing, no back-face culling.
 
+:meth:`MeshRenderer.render` also turns the hands before it draws them (``view``: ``SMPLRenderer.rotated``, vis_util.py:159-188, about the
+middle of the drawn hands' bounding box), paints them per vertex (``vertex_colors``; :func:`penetration_colors` makes the colours from
+the collision module's per-vertex penetration depth) and returns the coverage mask (``return_alpha``); :meth:`MeshRenderer.render_views`
+stacks several views, :func:`rotated` is the single-sample numpy form.
+
 :class:`MeshRenderer` is the batched device interface; :func:`render_together`, :func:`render_mesh_to_image`, :func:`render`,
 :func:`draw_keypoints` and :func:`recover_img` keep the reference's single-sample numpy signatures and BGR conventions.  No CPU
 fallback: without the library or a GPU the calls raise.
@@ -139,6 +144,28 @@ def _lights_struct():
     return L
 
 
+def view_rotation(axis, deg):
+    """The (3,3) float64 matrix ``cv2.Rodrigues`` gives ``SMPLRenderer.rotated`` (vis_util.py:171-176) for a turn of ``deg`` degrees
+    about 'y', 'x' or -- any other value -- z, written out for a coordinate axis (cos, +-sin, 0 and 1, nothing summed).  The renderer
+    multiplies a row vector with it: ``(p - c) R + c``."""
+    t = np.radians(float(deg))
+    c, s = np.cos(t), np.sin(t)
+    if axis == "y":
+        return np.array([[c, 0.0, s], [0.0, 1.0, 0.0], [-s, 0.0, c]])
+    if axis == "x":
+        return np.array([[1.0, 0.0, 0.0], [0.0, c, -s], [0.0, s, c]])
+    return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+
+
+def _view_matrix(view):
+    """``view`` as a float32 array (3,3) or (B,3,3): a matrix, or an ``(axis, deg)`` pair."""
+    if isinstance(view, (tuple, list)) and len(view) == 2 and isinstance(view[0], str):
+        return view_rotation(view[0], view[1]).astype(np.float32)
+    if isinstance(view, torch.Tensor):
+        return view.detach().to(torch.float32)
+    return np.asarray(view, np.float32)
+
+
 class MeshRenderer:
     """Batched renderer of a right / left hand pair.  ``faces_right`` (nF0,3), ``faces_left`` (nF1,3) or None; the merged table is
     ``concat(faces_right, faces_left + n_verts_right)`` (evaluator.py:212-213), built once with its incident-face CSR."""
@@ -157,6 +184,20 @@ class MeshRenderer:
         self.face_split = fr.shape[0]
         self.csr_offsets, self.csr_ids = build_csr(self.faces, self.n_verts)
         self._dev = None
+        self._views = {}
+
+    def _view_on_device(self, view, device):
+        """The float32 matrix of ``view`` on ``device``; that of an ``(axis, deg)`` pair is uploaded once and kept (an upload per call
+        would make the host wait for the stream)."""
+        pair = isinstance(view, (tuple, list)) and len(view) == 2 and isinstance(view[0], str)
+        key = (view[0], float(view[1]), device) if pair else None
+        if key in self._views:
+            return self._views[key]
+        rot = _view_matrix(view)
+        rot = (rot if isinstance(rot, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(rot))).to(device).contiguous()
+        if pair:
+            self._views[key] = rot
+        return rot
 
     def _tables(self, device):
         if self._dev is None or self._dev[0] != device:
@@ -164,12 +205,19 @@ class MeshRenderer:
             self._dev = (device, up(self.faces), up(self.csr_offsets), up(self.csr_ids))
         return self._dev[1:]
 
-    def render(self, verts_right, verts_left, cam, background=None, present=None, colors=None, return_face_ids=False, size=None):
+    def render(self, verts_right, verts_left, cam, background=None, present=None, colors=None, return_face_ids=False, size=None, *,
+               view=None, pivot=None, vertex_colors=None, return_alpha=False):
         """Device tensors: ``verts_right`` (B,nV0,3), ``verts_left`` (B,nV1,3) or None, fp32 or fp16; ``cam`` (B,3) = [s, tx, ty];
         ``background`` (B,S,S,3) uint8 or None (white; then ``size`` = S); ``present`` (B,2) marks the hands to draw (default: those
         given); ``colors`` (B,2,3) or (2,3) albedo per hand in the image's channel order (default right ``light_green``, left
         ``light_blue`` of render_color_utils.colors, BGR).  Returns the (B,S,S,3) uint8 image, with ``return_face_ids`` also the
-        (B,S,S) int32 visible face per pixel (-1 = none).  Asynchronous on the current stream."""
+        (B,S,S) int32 visible face per pixel (-1 = none).  Asynchronous on the current stream.
+
+        Keyword only: ``view`` a (3,3) or (B,3,3) matrix R or an ``(axis, deg)`` pair (:func:`view_rotation`): the hands are drawn at
+        ``(v - c) R + c`` (``ihmr_view_vertices``), c = ``pivot`` (B,3) or (3,), by default the middle of the bounding box of the hands
+        that are drawn; None draws them where they are (no transform: an identity matrix would round).  ``vertex_colors`` (B,nV,3)
+        float32: one albedo per vertex of the merged mesh instead of ``colors`` (``ihmr_paint_meshes``).  ``return_alpha`` appends a
+        (B,S,S) uint8 mask, 255 where a face is visible, to what is returned."""
         hip.require_gpu()
         dev = verts_right.device
         B = verts_right.shape[0]
@@ -203,15 +251,55 @@ class MeshRenderer:
         pres = None if present is None else torch.as_tensor(present).to(dev, torch.uint8).reshape(B, 2).contiguous()
         faces, off, ids = self._tables(dev)
         L = hip.lib()
+        if view is not None:
+            rot = self._view_on_device(view, dev)
+            if tuple(rot.shape) not in ((3, 3), (B, 3, 3)):
+                raise ValueError(f"view must be a (3,3) or ({B},3,3) matrix or an (axis, deg) pair, not {tuple(rot.shape)}")
+            if pivot is not None:
+                pivot = torch.as_tensor(pivot, dtype=torch.float32).to(dev)
+                pivot = (pivot.reshape(1, 3).expand(B, 3) if pivot.dim() == 1 else pivot.reshape(B, 3)).contiguous()
+            turned = torch.empty_like(verts)
+            hip.check(L.ihmr_view_vertices(hip.ptr(verts), hip.ptr(pres), self.n_verts, self.n_verts_right, hip.ptr(rot), int(rot.dim() == 3),
+                                           hip.ptr(pivot), hip.ptr(turned), B, hip.stream_ptr()), "ihmr_view_vertices")
+            verts = turned
+        elif pivot is not None:
+            raise ValueError("a pivot without a view")
         ws = torch.empty(L.ihmr_render_workspace_bytes(B, self.n_verts), dtype=torch.uint8, device=dev)
         out = torch.empty(B, S, S, 3, dtype=torch.uint8, device=dev)
-        fid = torch.empty(B, S, S, dtype=torch.int32, device=dev) if return_face_ids else None
+        fid = torch.empty(B, S, S, dtype=torch.int32, device=dev) if return_face_ids or return_alpha else None
         lights = _lights_struct()
-        hip.check(L.ihmr_render_meshes(hip.ptr(verts), hip.ptr(faces), hip.ptr(off), hip.ptr(ids), self.n_verts, self.faces.shape[0],
-                                       self.face_split, hip.ptr(pres), hip.ptr(albedo), hip.ptr(cam), C.byref(lights),
-                                       hip.ptr(background), S, hip.ptr(out), hip.ptr(fid), hip.ptr(ws), B, hip.stream_ptr()),
-                  "ihmr_render_meshes")
-        return (out, fid) if return_face_ids else out
+        if vertex_colors is not None:
+            vc = f32(vertex_colors).contiguous()
+            if vc.shape != (B, self.n_verts, 3):
+                raise ValueError(f"vertex_colors {tuple(vc.shape)} is not ({B}, {self.n_verts}, 3)")
+            draw, name, albedo = L.ihmr_paint_meshes, "ihmr_paint_meshes", vc
+        else:
+            draw, name = L.ihmr_render_meshes, "ihmr_render_meshes"
+        hip.check(draw(hip.ptr(verts), hip.ptr(faces), hip.ptr(off), hip.ptr(ids), self.n_verts, self.faces.shape[0],
+                       self.face_split, hip.ptr(pres), hip.ptr(albedo), hip.ptr(cam), C.byref(lights),
+                       hip.ptr(background), S, hip.ptr(out), hip.ptr(fid), hip.ptr(ws), B, hip.stream_ptr()), name)
+        ret = (out,) + ((fid,) if return_face_ids else ()) + (((fid >= 0).to(torch.uint8) * 255,) if return_alpha else ())
+        return ret if len(ret) > 1 else out
+
+    def render_views(self, verts_right, verts_left, cam, views, background=None, present=None, colors=None, size=None, *, pivot=None,
+                     vertex_colors=None):
+        """(B,V,S,S,3) uint8: one render per entry of ``views``.  An entry None is the camera's own view, drawn over ``background``
+        (white without one); any other entry (what :meth:`render` takes as ``view``) is drawn on white, as ``SMPLRenderer.rotated`` is
+        called without an image.  The other arguments are those of :meth:`render`."""
+        views = list(views)
+        if not views:
+            raise ValueError("no views")
+        if background is None and size is None:
+            raise ValueError("without a background the image size must be given")
+        S = int(size) if background is None else background.shape[1]
+        out = [self.render(verts_right, verts_left, cam, background if v is None else None, present=present, colors=colors, size=S,
+                           view=v, pivot=None if v is None else pivot, vertex_colors=vertex_colors) for v in views]
+        B, V, row = out[0].shape[0], len(out), S * S * 3
+        if row % 4:
+            return torch.stack(out, dim=1)
+        # whole dwords: the images are put side by side as 32-bit words (a byte-wise device copy is several times slower)
+        words = torch.stack([o.reshape(B, row).view(torch.int32) for o in out], dim=1)
+        return words.view(torch.uint8).reshape(B, V, S, S, 3)
 
 
 def draw_keypoints_device(img, kps, weight, color):
@@ -227,6 +315,36 @@ def draw_keypoints_device(img, kps, weight, color):
     hip.check(hip.lib().ihmr_draw_keypoints(hip.ptr(img), hip.ptr(kps), hip.ptr(weight), bytes(int(c) & 255 for c in color), B, S, K,
                                             hip.stream_ptr()), "ihmr_draw_keypoints")
     return img
+
+
+def penetration_colors(depth, colors=None, hot=(0, 0, 1), lo=0.0, hi=0.005, layout="collision", n_split=None):
+    """Per-vertex albedo (B,nV,3) float32 for ``vertex_colors`` from a per-vertex penetration depth (``ihmr_heat_colours``): the hand's
+    colour of ``colors`` ((2,3) or (B,2,3), default ``light_green`` / ``light_blue``) where the depth is ``lo`` or less (or NaN), ``hot``
+    (image channel order: the default is red in BGR) from ``hi`` on, a linear blend between.  ``depth`` (B,nV) device tensor in metres;
+    ``layout`` "collision" is the order of ``collision_loss_origin_scale`` / ``SDFLoss``'s ``origin_scale`` (entry h*778 + v was sampled
+    at vertex v of hand 1 - h), "vertex" means entry k belongs to vertex k of the merged mesh.  Vertices below ``n_split`` (default
+    half of them) belong to the right hand."""
+    hip.require_gpu()
+    if layout not in ("collision", "vertex"):
+        raise ValueError(f"layout {layout!r} is neither 'collision' nor 'vertex'")
+    if depth.dim() != 2:
+        raise ValueError("depth must be (B, n_verts)")
+    dev = depth.device
+    depth = depth.detach().to(torch.float32).contiguous()
+    B, nV = depth.shape
+    n_split = nV // 2 if n_split is None else int(n_split)
+    if colors is None:
+        colors = torch.tensor([COLORS["light_green"], COLORS["light_blue"]], dtype=torch.float32)
+    colors = torch.as_tensor(colors, dtype=torch.float32).to(dev)
+    albedo = (colors.reshape(1, 2, 3).expand(B, 2, 3) if colors.dim() == 2 else colors.reshape(B, 2, 3)).contiguous()
+    out = torch.empty(B, nV, 3, dtype=torch.float32, device=dev)
+    hot3 = (C.c_float * 3)(*[float(h) for h in hot])
+    rc = hip.lib().ihmr_heat_colours(hip.ptr(depth), hip.ptr(albedo), hot3, float(lo), float(hi), nV, n_split, int(layout == "collision"),
+                                     hip.ptr(out), B, hip.stream_ptr())
+    if rc == -1:
+        raise ValueError(f"ihmr_heat_colours refused lo = {lo}, hi = {hi}, n_verts = {nV}, n_split = {n_split}, layout = {layout!r}")
+    hip.check(rc, "ihmr_heat_colours")
+    return out
 
 
 # ------------------------------------------------------------------------------- the reference's single-sample functions (numpy)
@@ -266,6 +384,24 @@ def render_mesh_to_image(inputSize, image, cam, vert, face):
 def render(verts, faces, cam, inputSize, image):
     """vis_util.py:74-75."""
     return render_mesh_to_image(inputSize, image, cam, verts, faces)
+
+
+def rotated(verts, faces, deg, cam, inputSize, axis='y', img=None, do_alpha=True):
+    """``SMPLRenderer.rotated`` (vis_util.py:159-188) for one hand: ``verts`` turned by ``deg`` degrees about ``axis`` around the middle
+    of their bounding box (the reference: their mean), drawn in ``light_green`` with the camera ``cam`` = [s, tx, ty] over ``img``
+    (uint8 HWC) or white -> (S,S,3) uint8, with ``do_alpha`` (S,S,4).  The fourth channel is 255 everywhere with ``img``
+    (``append_alpha``); without it 255 exactly where a face is visible (``get_alpha`` keys on the pixel being white instead)."""
+    hip.require_gpu()
+    r = MeshRenderer(faces, None, verts.shape[0])
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32))).cuda()
+    colors = np.array([SINGLE_HAND_COLOR, SINGLE_HAND_COLOR])
+    out, alpha = r.render(dev(verts)[None], None, dev(np.asarray(cam)[:3])[None], _background_bytes(img, inputSize), colors=dev(colors),
+                          size=inputSize, view=(axis, deg), return_alpha=True)
+    out = out[0].cpu().numpy()
+    if not do_alpha:
+        return out
+    a = np.full(out.shape[:2], 255, np.uint8) if img is not None else alpha[0].cpu().numpy()
+    return np.concatenate((out, a[:, :, None]), axis=2)
 
 
 def draw_keypoints(image, kps, kps_weight, color=(0, 0, 255), img_size=224):

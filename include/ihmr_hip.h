@@ -526,6 +526,33 @@ int ihmr_render_meshes(const float* verts, const int32_t* faces, const int32_t* 
 /* img (B,S,S,3) bytes, in place;  kps (B,K,2) float32 in [-1,1];  weight (B,K) float32: a keypoint is drawn iff its weight > 0, in
  * order (a later one overwrites an earlier one), as a filled disc of radius 3 clipped at the border;  colour: 3 bytes (host). */
 int ihmr_draw_keypoints(uint8_t* img, const float* kps, const float* weight, const uint8_t* colour, int B, int S, int K, void* stream);
+/* Rotated views and the penetration heat map: SMPLRenderer.rotated and get_alpha / append_alpha of utils/vis_util.py:159-188,258-275,
+ * which nothing in the reference calls.  The arithmetic is stated in csrc/render_pure.h (rnd_view_point, rnd_bbox_mid, rnd_heat_colour).
+ * All three are asynchronous on `stream`; none allocates, none uses scratch memory or float atomics.
+ *
+ * ihmr_view_vertices: out[b,v] = (verts[b,v] - c_b) R_b + c_b (a row vector times the matrix, as np.dot(verts - center, around) + center).
+ * verts (B,n_verts,3) float32, model space;  rot (3,3) float32, or (B,3,3) when rot_per_sample is 1;  pivot (B,3), or NULL for the
+ * middle of the bounding box of the finite vertices of the hands that are drawn (present (B,2) bytes or NULL = both; vertex v belongs
+ * to hand 0 iff v < n_split; the origin when there is no such vertex -- the reference takes the vertex mean: DESIGN.md section 8.1);
+ * out (B,n_verts,3) float32 must not overlap verts (refused).  One launch, one workgroup per sample; every vertex of a sample is
+ * transformed, drawn or not.  ihmr_render_meshes / ihmr_paint_meshes then draw `out` with the sample's own camera.  An unrotated view
+ * is a call that is not made: the identity matrix does not give the vertices back bit for bit. */
+int ihmr_view_vertices(const float* verts, const uint8_t* present, int n_verts, int n_split, const float* rot, int rot_per_sample,
+                       const float* pivot, float* out, int B, void* stream);
+/* out[b,v] = base + t (hot - base), t = clamp01((d - lo) / (hi - lo)) (0 for a NaN depth): depth (B,n_verts) float32;  albedo (B,2,3)
+ * the base colour per sample and hand (vertex v belongs to hand 0 iff v < n_split);  hot: three floats (host);  lo < hi, both finite
+ * (otherwise refused);  out (B,n_verts,3) float32, the vertex_albedo of ihmr_paint_meshes.  layout 0: entry k is the depth at vertex k.
+ * layout 1: the order of ihmr_sdf_collision's origin_scale (entry h*n_split + k was sampled at vertex k of hand 1 - h), so vertex
+ * v < n_split reads entry n_split + v and vertex v >= n_split reads entry v - n_split; refused unless n_verts == 2 * n_split. */
+int ihmr_heat_colours(const float* depth, const float* albedo, const float* hot, float lo, float hi, int n_verts, int n_split, int layout,
+                      float* out, int B, void* stream);
+/* ihmr_render_meshes with one albedo per vertex: vertex_albedo (B,n_verts,3) float32.  Every other argument, the workspace
+ * (ihmr_render_workspace_bytes), the two launches and the raster kernel are those of ihmr_render_meshes; with every vertex given its
+ * hand's colour the result is that call's, byte for byte. */
+int ihmr_paint_meshes(const float* verts, const int32_t* faces, const int32_t* csr_offsets, const int32_t* csr_ids, int n_verts,
+                      int n_faces, int face_split, const uint8_t* present, const float* vertex_albedo, const float* cam,
+                      const ihmr_render_lights* lights, const uint8_t* background, int S, uint8_t* out_img, int32_t* out_face_ids,
+                      void* workspace, int B, void* stream);
 
 /* per-kernel timing hook for bench.py -- the ONE piece of mutable PROCESS-GLOBAL state of this library (everything else is stateless
  * apart from the model handle and a per-device cache of the CU count, relaxed atomics: concurrent first calls store the same value): the timer pointer and the pending event pairs are shared by every stream and every thread of the process

@@ -9,8 +9,13 @@ synchronise, five repetitions, median and min-max):
     read back), computed from the shapes, over the time, as a fraction of the 8 TB/s peak;
   * the numpy restatement (tests/render_ref.py) for ONE image of the same scene on the CPU, as the baseline.
 
-    python scripts/bench_render.py [batch] [json output path]
+With `--views N` the S = 448 batch is also drawn through `MeshRenderer.render_views` with N turned views next to the camera's (one
+`ihmr_view_vertices` launch and one more render each); with `--collision_map` it is also drawn painted by a per-vertex penetration depth
+(`penetration_colors` = one `ihmr_heat_colours` launch, then `ihmr_paint_meshes`).  Both alternate with the plain render in the same windows.
+
+    python scripts/bench_render.py [batch] [json output path] [--views N] [--collision_map]
 """
+import argparse
 import json
 import os
 import statistics
@@ -27,7 +32,13 @@ import render_cases as RC  # noqa: E402  (the deep-overlap synthetic hands of th
 import render_ref as R  # noqa: E402
 from ihmr_amd import render  # noqa: E402
 
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+ap = argparse.ArgumentParser()
+ap.add_argument("batch", nargs="?", type=int, default=64)
+ap.add_argument("json_path", nargs="?", default=None)
+ap.add_argument("--views", type=int, default=0, help="number of turned views drawn next to the camera's view")
+ap.add_argument("--collision_map", action="store_true", help="also draw the batch painted by a per-vertex penetration depth")
+args = ap.parse_args()
+B = args.batch
 WINDOW, REPS, HBM_PEAK = 50, 5, 8.0e12
 rng = np.random.RandomState(0)
 base = RC.hand_verts()
@@ -42,7 +53,13 @@ runs = {}
 for S in (448, 224):
     runs[f"S = {S}"] = lambda S=S: renderer.render(verts[:, :778], verts[:, 778:], cam, bgs[S])
     runs[f"S = {S}, with face ids"] = lambda S=S: renderer.render(verts[:, :778], verts[:, 778:], cam, bgs[S], return_face_ids=True)
-
+if args.views > 0:
+    view_list = [None] + [("yxz"[k % 3], 90.0 + 35.0 * (k // 3)) for k in range(args.views)]
+    runs[f"S = 448, {args.views} extra view(s)"] = lambda: renderer.render_views(verts[:, :778], verts[:, 778:], cam, view_list, bgs[448])
+if args.collision_map:
+    depth = torch.from_numpy(rng.uniform(-0.002, 0.008, (B, 1556)).astype(np.float32)).cuda()
+    runs["S = 448, heat map"] = lambda: renderer.render(verts[:, :778], verts[:, 778:], cam, bgs[448],
+                                                        vertex_colors=render.penetration_colors(depth))
 
 
 def entry_point_alone(S):
@@ -86,10 +103,13 @@ for S in (448, 224):
     covered[S] = float((ids >= 0).float().mean().item())
 
 
-def launch_bytes(S, with_ids):
+def launch_bytes(S, with_ids, views=0, heat=False):
     tables = B * 1556 * 12 + 3076 * 12 + 1557 * 4 + 3 * 3076 * 4 + B * (12 + 24 + 2)       # vertices, faces, CSR, camera / albedo / present
     workspace = 2 * B * 1556 * 24                                                          # written by the vertex launch, read by the raster launch
-    return 2 * B * S * S * 3 + (B * S * S * 4 if with_ids else 0) + tables + workspace
+    one = 2 * B * S * S * 3 + (B * S * S * 4 if with_ids else 0) + tables + workspace
+    turned = B * S * S * 3 + tables + workspace + 2 * B * 1556 * 12                        # on white: no background read; vertices read and written
+    painted = B * 1556 * 4 + 2 * B * 1556 * 12                                             # depth read, colours written and read back
+    return one + views * turned + (painted if heat else 0)
 
 
 t0 = time.perf_counter()
@@ -100,12 +120,12 @@ res = dict(batch=B, window=WINDOW, repetitions=REPS, covered_fraction=covered, c
 for k, v in times.items():
     S, with_ids = (448 if "448" in k else 224), "face ids" in k
     med = statistics.median(v)
-    nbytes = launch_bytes(S, with_ids)
+    nbytes = launch_bytes(S, with_ids, args.views if "extra view" in k else 0, "heat map" in k)
     res["configs"][k] = dict(median_ms=med, min_ms=min(v), max_ms=max(v), hbm_bytes=nbytes, fraction_of_hbm_peak=nbytes / (med * 1e-3) / HBM_PEAK)
     print(f"{k:28s} {med:.4f} ms per batch of {B} (min {min(v):.4f}, max {max(v):.4f}); {nbytes / 1e6:.1f} MB -> "
           f"{nbytes / (med * 1e-3) / 1e12:.3f} TB/s = {100 * nbytes / (med * 1e-3) / HBM_PEAK:.1f} % of the 8 TB/s peak")
 print(f"covered pixels: {covered};  numpy restatement, one 448 x 448 image on the CPU: {cpu_ms:.0f} ms")
 print(json.dumps(res))
-if len(sys.argv) > 2:
-    with open(sys.argv[2], "w") as fh:
+if args.json_path:
+    with open(args.json_path, "w") as fh:
         json.dump(res, fh)
