@@ -21,6 +21,7 @@
 #include "encoder.h"
 #include "encoder_bf16.h"
 #include "evaluate.h"
+#include "volume.h"
 #include "train.h"
 #include "train_conv.h"
 #include "copy_pack.h"
@@ -849,6 +850,13 @@ extern "C" int ihmr_eval_curve_verts(const float* pred_right, const float* pred_
 }
 
 // ------------------------------------------------------------------------------------------ IHMR-MLP training step
+extern "C" int ihmr_sdf_volume(const float* verts_a, const int32_t* faces_a, int n_verts_a, int n_faces_a, const float* verts_b,
+                               const int32_t* faces_b, int n_verts_b, int n_faces_b, int B, int subdiv, const uint8_t* keep, float* box,
+                               int32_t* status, uint32_t* counts, uint32_t* bits, void* stream) {
+    return vol_launch(verts_a, faces_a, n_verts_a, n_faces_a, verts_b, faces_b, n_verts_b, n_faces_b, B, subdiv, keep, box, status,
+                      counts, bits, (hipStream_t)stream);
+}
+
 extern "C" int ihmr_mlp_train_grad(const ihmr_mano* m, const ihmr_mano* m_left, const ihmr_opt_io* io, int B,
                                    const ihmr_opt_weights* w, const ihmr_train_weights* tw, const float* gt_pose,
                                    const float* gt_shape, const float* params_weight, const float* init_shape,

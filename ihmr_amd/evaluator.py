@@ -19,6 +19,11 @@ tau) and its AUC for five error populations, the mesh F-score at 5 mm / 15 mm an
 (:func:`calc_collision_auc`).  None of them follows from the sums above; all of them follow from COUNTS per threshold, which add over
 batches and ranks (:meth:`Evaluator.curve_sums`, :meth:`Evaluator.curve_metrics_from_sums`).  ``update_device_curves`` /
 ``update_device_curve_verts`` count on the GPU (``ihmr_eval_curve_joints`` / ``ihmr_eval_curve_verts``).
+
+``Evaluator(volume_metric=True)`` adds the two-hand intersection volume in cm^3 (``pen_volume``, ``pen_rate``): the voxels of one grid
+common to both hands that lie inside both (``ihmr_sdf_volume``), where ``collision_ave`` / ``collision_max`` are
+depths read at vertices.  It is device-only (:meth:`Evaluator.update_device_volume`, :meth:`Evaluator.volume_sums`): no record, no
+pickled file and none of the other sums changes with it.
 """
 from __future__ import annotations
 
@@ -243,7 +248,7 @@ def write_image_bgr(path, img):
 
 class Evaluator:
     def __init__(self, mano_models=None, data_list=None, image_root="", inputSize=224, pa_metrics=False, curve_metrics=False,
-                 thresholds=None, f_thresholds=None):
+                 thresholds=None, f_thresholds=None, volume_metric=False, volume_subdiv=2):
         self.pa_metrics = pa_metrics    # records carry the Procrustes-aligned errors too (off: records and files as before)
         # records carry what the PCK curves, the F-scores and the collision AUC are counted from (off: records and files as before)
         self.curve_metrics = curve_metrics
@@ -267,8 +272,15 @@ class Evaluator:
         self._device_pa_vert_parts = []   # (B,2) float64 [sum of aligned per-vertex errors, count]
         self._device_curve_parts = []     # (B,3,T+1) float64 counts of the joint populations
         self._device_curve_vert_parts = []   # ((B,2,T+1) counts, (B,2,2,2,F) per-hand F counts, (B,2,2) hand counted and kept)
+        if volume_metric:               # off: no attribute is added, a default Evaluator pickles byte for byte as before
+            if volume_subdiv not in (1, 2, 4):
+                raise ValueError(f"volume_subdiv = {volume_subdiv!r}: 1, 2 or 4")
+            self.volume_metric, self.volume_subdiv = True, int(volume_subdiv)
+            self._device_volume_parts = []   # (B,4) float64 [cm^3, interacting and kept, of those with count > 0, invalid]
 
     def clear(self):
+        if "_device_volume_parts" in self.__dict__:
+            self._device_volume_parts = []
         self.pred_results = []
         self._device_parts = []
         self._device_vert_parts = []
@@ -421,6 +433,49 @@ class Evaluator:
         if keep is not None:      # a selection, as in update_device
             out = torch.where(keep.to(dev, torch.bool)[:, None], out, torch.zeros_like(out))
         self._device_vert_parts.append(out)
+
+    def update_device_volume(self, pred_right, pred_left, keep=None, interacting=None):
+        """Two-hand intersection volume of one batch from device tensors (``ihmr_sdf_volume`` through
+        :func:`ihmr_amd.sdf.penetration_volume`, ``Evaluator(volume_metric=True, volume_subdiv=2)``): the two predicted meshes
+        (B,778,3), the MANO faces with the wrist closed.  ``keep`` (B) bool masks out padding duplicates, ``interacting`` (B) bool =
+        hand_type == 'interacting' (default all); a sample outside either mask is not ray-traced and counts nowhere.  Accumulates
+        lazily, see :meth:`volume_sums`.  The metric is device-only: there is no host-records path, the records, ``metric_sums()``,
+        ``pa_metric_sums()``, ``curve_sums()`` and pickled files carry nothing of it."""
+        import torch
+
+        from . import hip, sdf
+        if not getattr(self, "volume_metric", False):
+            raise RuntimeError("update_device_volume needs Evaluator(volume_metric=True)")
+        hip.require_gpu()
+        assert self.right_hand_faces is not None and self.left_hand_faces is not None, "Evaluator needs the MANO models' faces"
+        B, dev = pred_right.shape[0], pred_right.device
+        use = torch.ones(B, dtype=torch.bool, device=dev)
+        for mask in (keep, interacting):
+            if mask is not None:
+                use = use & mask.to(dev, torch.bool)
+        volume, _, _, status = sdf.penetration_volume(pred_right, pred_left, self.right_hand_faces, self.left_hand_faces,
+                                                      subdiv=self.volume_subdiv, keep=use)
+        n = use.to(torch.float64)
+        zero = torch.zeros_like(n)
+        self._device_volume_parts.append(torch.stack([volume * 1e6, n, torch.where(volume > 0, n, zero),
+                                                      torch.where(status == 2, n, zero)], dim=1))
+
+    def volume_sums(self):
+        """[sum of the intersection volumes in cm^3, interacting samples kept, those of them with a voxel inside both hands, those of
+        them the kernel called invalid] (float64, additive over batches and ranks): what :meth:`update_device_volume` left on the
+        device.  Zeros for an Evaluator without ``volume_metric``."""
+        sums = np.zeros(4, dtype=np.float64)
+        if getattr(self, "_device_volume_parts", None):
+            import torch
+            sums = sums + torch.cat(self._device_volume_parts, dim=0).sum(dim=0).cpu().numpy()
+        return sums
+
+    @staticmethod
+    def volume_metrics_from_sums(s):
+        """``pen_volume``: mean intersection volume [cm^3] over the interacting samples; ``pen_rate``: the share of them whose hands
+        intersect at all.  NaN where no sample was counted."""
+        d = lambda a, b: float(a / b) if b > 0 else float("nan")
+        return dict(pen_volume=d(s[0], s[1]), pen_rate=d(s[2], s[1]))
 
     def gather_pred(self, pred_results):
         self.pred_results += pred_results

@@ -45,12 +45,19 @@ def main(argv=None):
                          "and the collision AUCs of the per-sample max / mean penetration depth: counted on the device "
                          "(ihmr_eval_curve_joints), from the records under --host_eval.  IHMR-OPT exports no GT meshes: no vertex "
                          "curve, no F-score")
+    ap.add_argument("--volume_metric", action="store_true",
+                    help="also report pen_volume (mean two-hand intersection volume in cm^3 over the interacting samples) and pen_rate "
+                         "(the share of them whose hands intersect): counted on the device (ihmr_sdf_volume); there is no host path, "
+                         "so not together with --host_eval")
+    ap.add_argument("--volume_subdiv", type=int, default=2, choices=[1, 2, 4], help="the volume grid is (32 * volume_subdiv)^3")
     ap.add_argument("--streams", type=int, default=1,
                     help="model instances driven side by side on their own HIP streams (2 x --fuse_batches 8 saturates one MI355X; "
                          "more than 4 need GPU_MAX_HW_QUEUES raised in the environment)")
     ap.add_argument("--fuse_batches", type=int, default=1,
                     help="consecutive batches carried by one launch sequence (per-sample results identical to separate batches)")
     args = ap.parse_args(argv)
+    if args.volume_metric and args.host_eval:
+        ap.error("--volume_metric is counted on the device only: it cannot be combined with --host_eval")
 
     rank, world = D.init_dist()
     if world == 1:
@@ -66,7 +73,8 @@ def main(argv=None):
     singles = [model] + [None] * (S - 1)                                      # remainder of fewer than G batches: batch by batch
     main_stream = torch.cuda.current_stream()
     streams = [torch.cuda.Stream() for _ in range(S)] if S > 1 else [main_stream]
-    evaluator = Evaluator(model.mano_models, pa_metrics=args.pa_metrics, curve_metrics=args.curve_metrics)
+    evaluator = Evaluator(model.mano_models, pa_metrics=args.pa_metrics, curve_metrics=args.curve_metrics,
+                          volume_metric=args.volume_metric, volume_subdiv=args.volume_subdiv)
     fwd = lambda p, s, t: two_hand.forward_from_packed(model.mano_models["right"], p.cuda(), s.cuda(), t.cuda())[2]
 
     idx, is_pad = D.shard_indices(args.num_samples, args.batchSize, rank, world)
@@ -118,27 +126,33 @@ def main(argv=None):
                         evaluator.update_device_pa(mdl.pred_joints_3d, mdl.buf["gt_joints_3d"], keep=torch.from_numpy(~pad))
                     if args.curve_metrics:
                         evaluator.update_device_curves(mdl.pred_joints_3d, mdl.buf["gt_joints_3d"], keep=torch.from_numpy(~pad))
+                    if args.volume_metric:
+                        evaluator.update_device_volume(mdl.pred_right_hand_verts, mdl.pred_left_hand_verts, keep=torch.from_numpy(~pad))
         for _, st, *_ in jobs:
             main_stream.wait_stream(st)                 # the next round's data generation reuses the instances' MANO handles
     torch.cuda.synchronize()
     base = evaluator.metric_sums()
     n_base = len(base)
-    # with --pa_metrics / --curve_metrics all metric vectors travel in the one all-reduce
-    parts = [base] + ([evaluator.pa_metric_sums()] if args.pa_metrics else []) + ([evaluator.curve_sums()] if args.curve_metrics else [])
+    # with --pa_metrics / --volume_metric / --curve_metrics all metric vectors travel in the one all-reduce
+    parts = ([base] + ([evaluator.pa_metric_sums()] if args.pa_metrics else []) + ([evaluator.volume_sums()] if args.volume_metric else [])
+             + ([evaluator.curve_sums()] if args.curve_metrics else []))
     sums = D.reduce_metrics(np.concatenate(parts))
     elapsed = time.time() - t0
     m = Evaluator.metrics_from_sums(sums[:n_base])
     n_pa = 6 if args.pa_metrics else 0
+    n_vol = 4 if args.volume_metric else 0
     if args.pa_metrics:
         m.update(Evaluator.pa_metrics_from_sums(sums[n_base:n_base + n_pa]))
+    if args.volume_metric:
+        m.update(Evaluator.volume_metrics_from_sums(sums[n_base + n_pa:n_base + n_pa + n_vol]))
     curve_keys = ()
     if args.curve_metrics:
-        c = Evaluator.curve_metrics_from_sums(sums[n_base + n_pa:])
+        c = Evaluator.curve_metrics_from_sums(sums[n_base + n_pa + n_vol:])
         curve_keys = ("auc_j3d", "auc_pa_inter_j3d", "auc_pa_j3d", "collision_auc_max", "collision_auc_ave")
         m.update({k: c[k] for k in curve_keys})
         m.update({k: c[k].tolist() for k in ("pck_j3d", "pck_pa_inter_j3d", "pck_pa_j3d")})       # the curves go into the JSON line
     if rank == 0:
-        for k in ("mpjpe_3d", "inter_mpjpe_3d", "collision_ave", "collision_max") + (("pa_inter_mpjpe_3d", "pa_mpjpe_3d") if args.pa_metrics else ()) + curve_keys:
+        for k in ("mpjpe_3d", "inter_mpjpe_3d", "collision_ave", "collision_max") + (("pa_inter_mpjpe_3d", "pa_mpjpe_3d") if args.pa_metrics else ()) + (("pen_volume", "pen_rate") if args.volume_metric else ()) + curve_keys:
             print(f"{k} : {m[k]:.3f} (optimize)")
         print(json.dumps(dict(num_samples=args.num_samples, world=world, seconds=elapsed, **m)))
     if torch.distributed.is_available() and torch.distributed.is_initialized():

@@ -103,6 +103,97 @@ class SDFLoss(nn.Module):
         return loss
 
 
+# ------------------------------------------------------------------------------------------ two-hand intersection volume
+VOLUME_SUBDIVS = (1, 2, 4)
+
+
+def close_boundary(faces, n_verts):
+    """``faces`` (F,3) with every boundary loop closed by a triangle fan from the loop's lowest-numbered vertex.  No vertex is added; a
+    closed mesh comes back unchanged (a copy).  MANO is open at the wrist, one loop of 16 edges: 1538 -> 1552 faces.  A boundary edge is
+    a directed edge (a, b) of a face whose opposite (b, a) belongs to no face; a loop v0 -> v1 -> ... -> v_{m-1} -> v0 (v0 the lowest)
+    gets the faces (v0, v_{i+1}, v_i), i = 1 .. m-2, which run against it.  Pure integer host logic: the +x ray parity of
+    :func:`penetration_volume` is only right for closed meshes."""
+    f = np.asarray(faces)
+    if f.ndim != 2 or f.shape[1] != 3 or len(f) == 0 or f.min() < 0 or f.max() >= n_verts:
+        raise ValueError(f"faces: a (F,3) table of vertex ids in [0, {n_verts}) is needed")
+    e = np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]).astype(np.int64).tolist()
+    have = {(a, b) for a, b in e}
+    nxt = {}
+    for a, b in e:
+        if (b, a) not in have:
+            if a in nxt:
+                raise ValueError(f"vertex {a} starts two boundary edges: the boundary is no set of simple loops")
+            nxt[a] = b
+    added, left = [], set(nxt)
+    while left:
+        v0 = min(left)
+        loop, v = [v0], nxt[v0]
+        while v != v0:
+            if v not in nxt or len(loop) > len(nxt):
+                raise ValueError("an open boundary chain: the boundary is no set of simple loops")
+            loop.append(v)
+            v = nxt[v]
+        left -= set(loop)
+        added += [(v0, loop[i + 1], loop[i]) for i in range(1, len(loop) - 1)]
+    if not added:
+        return f.copy()
+    return np.concatenate([f, np.asarray(added, f.dtype)])
+
+
+_VOLUME_FACES = {}      # (device, bytes of the table, n_verts, closed) -> int32 device tensor
+
+
+def _volume_faces(faces, n_verts, close, dev):
+    """The (closed) face table on ``dev``, uploaded once per table and device."""
+    if torch.is_tensor(faces):
+        faces = faces.detach().cpu().numpy()
+    f = np.ascontiguousarray(np.asarray(faces).astype(np.int32))
+    key = (str(dev), f.tobytes(), int(n_verts), bool(close))
+    if key not in _VOLUME_FACES:
+        table = close_boundary(f, n_verts) if close else f
+        if table.ndim != 2 or table.shape[1] != 3 or not 1 <= len(table) <= hip.VOLUME_MAX_FACES:
+            raise ValueError(f"a face table of 1..{hip.VOLUME_MAX_FACES} triangles is needed, got shape {table.shape}")
+        _VOLUME_FACES[key] = torch.from_numpy(np.ascontiguousarray(table, np.int32)).to(dev)
+    return _VOLUME_FACES[key]
+
+
+def penetration_volume(verts_right, verts_left, faces_right, faces_left, subdiv=2, keep=None, close=True, return_bits=False):
+    """How much of one hand lies inside the other: the voxels of one common (32 * subdiv)^3 grid that are inside both meshes
+    (``ihmr_sdf_volume``; the definition is DESIGN.md section 8 and ``csrc/volume_pure.h``).  ``verts_*`` (B,n_verts,3) float32 device
+    tensors in metres, ``faces_*`` (F,3) integer tables (closed with :func:`close_boundary` unless ``close=False``; cached per device),
+    ``subdiv`` 1, 2 or 4, ``keep`` (B) bool: a sample left out costs no ray work and returns zeros.
+
+    Returns ``(volume, counts, box, status)``, with ``return_bits`` also ``bits``: ``volume`` (B,) float64 in m^3 =
+    ``count * (2 * (s / subdiv) / 32)^3`` formed in float64 from the float32 ``s``; ``counts`` (B,subdiv^3) int64 voxels per tile;
+    ``box`` (B,4) float32 centre and half side of the common cube; ``status`` (B,) int32, 0 counted | 1 empty (the vertex boxes do not
+    overlap) | 2 invalid (a non-finite vertex, or a cube of half side < 1e-5); ``bits`` (B,subdiv^3,1024) int32 words of the voxels
+    inside both.  Everything stays on the device; nothing synchronises."""
+    hip.require_gpu()
+    if subdiv not in VOLUME_SUBDIVS:
+        raise ValueError(f"subdiv = {subdiv!r}: 1, 2 or 4")
+    dev = verts_right.device
+    va, vb = verts_right.detach().to(dev, torch.float32).contiguous(), verts_left.detach().to(dev, torch.float32).contiguous()
+    if va.dim() != 3 or vb.dim() != 3 or va.shape[2] != 3 or vb.shape[2] != 3 or va.shape[0] != vb.shape[0] or va.shape[0] < 1:
+        raise ValueError(f"two (B,n_verts,3) vertex tensors of one batch size are needed, got {tuple(va.shape)} and {tuple(vb.shape)}")
+    B, na, nb = va.shape[0], va.shape[1], vb.shape[1]
+    if not (1 <= na <= hip.VOLUME_MAX_VERTS and 1 <= nb <= hip.VOLUME_MAX_VERTS):
+        raise ValueError(f"1..{hip.VOLUME_MAX_VERTS} vertices per mesh, got {na} and {nb}")
+    fa, fb = _volume_faces(faces_right, na, close, dev), _volume_faces(faces_left, nb, close, dev)
+    k = None if keep is None else keep.to(dev, torch.uint8).contiguous()
+    T = subdiv ** 3
+    box = torch.empty(B, 4, device=dev, dtype=torch.float32)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    counts = torch.empty(B, T, device=dev, dtype=torch.int32)           # (the words are unsigned; a tile holds at most 32768 voxels)
+    bits = torch.empty(B, T, 1024, device=dev, dtype=torch.int32) if return_bits else None
+    hip.check(hip.lib().ihmr_sdf_volume(va.data_ptr(), fa.data_ptr(), na, len(fa), vb.data_ptr(), fb.data_ptr(), nb, len(fb), B, subdiv,
+                                        None if k is None else k.data_ptr(), box.data_ptr(), status.data_ptr(), counts.data_ptr(),
+                                        None if bits is None else bits.data_ptr(), hip.stream_ptr()), "ihmr_sdf_volume")
+    counts = counts.to(torch.int64)
+    cell = 2.0 * (box[:, 3].to(torch.float64) / float(subdiv)) / 32.0        # s / subdiv is exact in either precision: a power of two
+    volume = counts.sum(dim=1).to(torch.float64) * (cell * cell * cell)
+    return (volume, counts, box, status, bits) if return_bits else (volume, counts, box, status)
+
+
 class SDFLoss_Single(nn.Module):  # imported but never used by the reference (loss_utils.py:13)
     def __init__(self, *a, **k):
         super().__init__()

@@ -351,6 +351,29 @@ int ihmr_eval_curve_verts(const float* pred_right, const float* pred_left, const
                           const double* thresholds, int T, const double* f_thresholds, int F, double* counts, double* f_counts,
                           double* nn_dist, void* stream);
 
+/* ------------------------------------------------------------------ two-hand intersection volume
+ * How much of one mesh lies inside the other, counted in voxels of ONE grid common to both (csrc/volume_pure.h states the arithmetic
+ * down to the float operation).  Per sample two CLOSED triangle meshes A and B: verts (B,n_verts,3) float32, one
+ * int32 face table (n_faces,3) per mesh shared by the batch (a mesh with an open boundary gives wrong parities for the columns through
+ * the hole: ihmr_amd.sdf.close_boundary caps MANO's wrist).  The common cube is the intersection of the two vertex boxes made cubic:
+ * box (B,4) = cx, cy, cz, s (half side).  It is cut into subdiv^3 tiles of 32^3 cell-centred voxels; a voxel is inside a mesh when the
+ * +x ray from its centre crosses an odd number of the mesh's triangles (the inside test of the collision grids).
+ *   status (B)             0 counted | 1 empty (the boxes do not overlap in some axis, hi <= lo) | 2 invalid (a non-finite vertex, or
+ *                          s < 1e-5).
+ *   counts (B,subdiv^3)    voxels inside both meshes per tile, tile = (tz * subdiv + ty) * subdiv + tx; every word is written.
+ *                          volume [m^3] = sum(counts) * (2 * (s / subdiv) / 32)^3.
+ *   bits (B,subdiv^3,1024) or NULL: per tile and column k * 32 + j the word whose bit i says that voxel (k, j, i) = (z, y, x) is
+ *                          inside both.
+ *   keep (B) or NULL       a sample with keep[b] == 0 costs no ray work.
+ * A sample that is not kept or not counted has zeros in box, counts and bits (status 0 when not kept).  A face that names a vertex
+ * outside [0, n_verts) is left out.  -1, nothing launched: a NULL required pointer, B < 1, subdiv not in {1, 2, 4}, n_verts outside
+ * 1..IHMR_VOLUME_MAX_VERTS, n_faces outside 1..IHMR_VOLUME_MAX_FACES.  No allocation, no synchronisation, no workspace. */
+#define IHMR_VOLUME_MAX_VERTS 1024
+#define IHMR_VOLUME_MAX_FACES 2048
+int ihmr_sdf_volume(const float* verts_a, const int32_t* faces_a, int n_verts_a, int n_faces_a,
+                    const float* verts_b, const int32_t* faces_b, int n_verts_b, int n_faces_b,
+                    int B, int subdiv, const uint8_t* keep, float* box, int32_t* status, uint32_t* counts, uint32_t* bits, void* stream);
+
 /* ------------------------------------------------------------------ packed transfers (round 5)
  * MLPModel.set_input (models/mlp_model.py:120-170) and get_pred_result (:702-719) move 17 + 13 small tensors one copy at a time; one
  * launch does a whole table of them.  A segment = a 2-D strided copy of 32-bit words: dst[r * dst_ld + c] = src[r * src_ld + c] for
