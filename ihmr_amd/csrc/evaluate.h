@@ -11,6 +11,76 @@
 #include "ihmr_common.h"
 #include "eval_pure.h"
 
+// ------------------------------------------------------------------------------------------ what the kernels of this file share
+// Every sum has one fixed order (lane-strided partials, xor butterfly over the wave, waves in index order), so a sample's result does
+// not depend on its place in the batch.
+__device__ __forceinline__ double wave_reduce_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// Joint j of sample b in the arithmetic type T of the caller: prediction, target and weight; zeros for the lanes j >= 42.
+template <typename T>
+__device__ __forceinline__ void load_joint(const float* __restrict__ pred, const float* __restrict__ gt, int b, int j,
+                                           T (&p)[3], T (&g)[3], T& w) {
+    p[0] = p[1] = p[2] = g[0] = g[1] = g[2] = w = (T)0;
+    if (j < 42) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { p[k] = (T)pred[((size_t)b * 42 + j) * 3 + k]; g[k] = (T)gt[((size_t)b * 42 + j) * 4 + k]; }
+        w = (T)gt[((size_t)b * 42 + j) * 4 + 3];
+    }
+}
+
+// Per-hand root-relative joint error (metric_utils.py:23-38), one wave, lane j: root 0 is subtracted for joints 0..20, then -- on the
+// already shifted copies a, g, which the caller gives up -- root 21.  Lane j counts (true, err = |a - g| / sc) when its hand's root and
+// its own weight are > 0; err is 0 otherwise.
+template <typename T>
+__device__ __forceinline__ bool root_relative_joint_error(int j, T w, T (&a)[3], T (&g)[3], T sc, T& err) {
+    bool counted = false;
+    err = (T)0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int root = 21 * h;
+        if (__shfl(w, root) > (T)0) {     // uniform over the wave
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { a[k] -= __shfl(a[k], root); g[k] -= __shfl(g[k], root); }
+            if (j >= root && j < root + 21 && w > (T)0) {
+                const T dx = a[0] - g[0], dy = a[1] - g[1], dz = a[2] - g[2];
+                err = sqrt((dx * dx + dy * dy) + dz * dz) / sc;
+                counted = true;
+            }
+        }
+    }
+    return counted;
+}
+
+// Sums over a workgroup of 256 (four waves) of the first K of a thread's float64 accumulators: butterfly over the wave, lane 0 to
+// part[wave][k], one barrier, the waves added as ((p0 + p1) + p2) + p3; every thread gets every sum.  The caller keeps a barrier
+// between these reads of `part` and its next write.
+template <int K, int N>
+__device__ __forceinline__ void block_sum_f64(const double (&acc)[N], double (*part)[10], double (&sum)[N]) {
+    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const double s = wave_reduce_sum_f64(acc[k]);
+        if (lane == 0) part[wave][k] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) sum[k] = ((part[0][k] + part[1][k]) + part[2][k]) + part[3][k];
+}
+
+// Hand h of sample b in the vertex kernels (grid = (B, 2)): its predicted and target mesh; true when the hand counts, i.e. a GT mesh
+// exists (mano_params_weight[b][h] > 0).
+__device__ __forceinline__ bool eval_hand(const float* __restrict__ pred_r, const float* __restrict__ pred_l, const float* __restrict__ gt_r,
+                                          const float* __restrict__ gt_l, const float* __restrict__ params_weight, int b, int h,
+                                          const float*& P, const float*& G) {
+    P = (h ? pred_l : pred_r) + (size_t)b * NV3;
+    G = (h ? gt_l : gt_r) + (size_t)b * NV3;
+    return params_weight[b * 2 + h] > 0.f;
+}
+
 // grid = B, block = 64: lane j < 42 owns joint j.  out (B,6) doubles:
 //   [0] sum of per-joint errors, [1] number of them, [2] sum of aligned ("inter") errors, [3] number of them,
 //   [4] mean penetration depth [mm], [5] max penetration depth [mm]  ([4],[5] = 0 and not counted unless interacting)
@@ -24,35 +94,15 @@ __global__ __launch_bounds__(64) void eval_metrics_kernel(const float* __restric
                                                           double* __restrict__ out) {
     const int b = blockIdx.x, j = threadIdx.x;
     const bool act = j < 42;
-    float a[3] = {0.f, 0.f, 0.f}, g[3] = {0.f, 0.f, 0.f}, w = 0.f;
-    if (act) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { a[k] = pred[((size_t)b * 42 + j) * 3 + k]; g[k] = gt[((size_t)b * 42 + j) * 4 + k]; }
-        w = gt[((size_t)b * 42 + j) * 4 + 3];
-    }
+    float a[3], g[3], w;
+    load_joint(pred, gt, b, j, a, g, w);
     const float sc = scale ? scale[b] : 1.0f;
     const float p0[3] = {a[0], a[1], a[2]}, g0[3] = {g[0], g[1], g[2]};   // un-shifted copies for the aligned error
 
-    // ---- per-hand MPJPE (metric_utils.py:23-38): root 0 for joints 0..20, then (on the already shifted copies) root 21
-    float err = 0.f, cnt = 0.f;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int root = 21 * h;
-        const float wr = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), root));
-        if (wr > 0.f) {     // uniform over the wave
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                a[k] -= __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a[k]), root));
-                g[k] -= __int_as_float(__builtin_amdgcn_readlane(__float_as_int(g[k]), root));
-            }
-            if (act && j >= root && j < root + 21 && w > 0.f) {
-                const float dx = a[0] - g[0], dy = a[1] - g[1], dz = a[2] - g[2];
-                err += sqrtf(dx * dx + dy * dy + dz * dz) / sc;
-                cnt += 1.f;
-            }
-        }
-    }
-    const double err_sum = (double)wave_reduce_sum(err), err_n = (double)wave_reduce_sum(cnt);
+    // ---- per-hand MPJPE (metric_utils.py:23-38)
+    float err;
+    const bool counted = root_relative_joint_error(j, w, a, g, sc, err);
+    const double err_sum = (double)wave_reduce_sum(err), err_n = (double)wave_reduce_sum(counted ? 1.f : 0.f);
 
     // ---- aligned error over all valid joints (metric_utils.py:107-143, no rotation): p' = (p - mean p) / std p * std g + mean g
     // The sample is left out when the SUM of its 42 weights is < 2.0 (metric_utils.py:131; EVP_MIN_WEIGHT_SUM), not by the number n of
@@ -88,9 +138,7 @@ __global__ __launch_bounds__(64) void eval_metrics_kernel(const float* __restric
             cnan |= x != x;
         }
     }
-    double cs = csum;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cs += __shfl_xor(cs, o);
+    const double cs = wave_reduce_sum_f64(csum);
     const float cm = __ballot(cnan) != 0ull ? NAN : wave_reduce_max(cmax);
     if (j == 0) {
         double* o = out + (size_t)b * 6;
@@ -114,12 +162,11 @@ __global__ __launch_bounds__(256) void eval_mpvpe_kernel(const float* __restrict
     __shared__ float root[6];
     const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
     double* o = hand_out + ((size_t)b * 2 + h) * 2;
-    if (!(params_weight[b * 2 + h] > 0.f)) {
+    const float *P, *G;
+    if (!eval_hand(pred_r, pred_l, gt_r, gt_l, params_weight, b, h, P, G)) {
         if (tid == 0) { o[0] = 0.0; o[1] = 0.0; }
         return;
     }
-    const float* P = (h ? pred_l : pred_r) + (size_t)b * NV3;
-    const float* G = (h ? gt_l : gt_r) + (size_t)b * NV3;
     const float* W = root_w + (size_t)h * NV;
     float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int v = tid; v < NV; v += 256) {
@@ -152,14 +199,7 @@ __global__ __launch_bounds__(256) void eval_mpvpe_kernel(const float* __restrict
 
 // ------------------------------------------------------------------------------------------ Procrustes-aligned errors (PA-MPJPE / PA-MPVPE)
 // utils/metric_utils.py:59-104 (calc_transform) and :120-143 (get_single_pa_inter_joints_error, use_rot=True), read with the points
-// in rows; the arithmetic and the set rules are csrc/eval_pure.h.  Inputs float32, every operation float64, no atomics; every sum has
-// one fixed order (lane-strided partials, xor butterfly over the wave, waves in index order), so a sample's result does not depend on
-// its place in the batch.
-__device__ __forceinline__ double wave_reduce_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+// in rows; the arithmetic and the set rules are csrc/eval_pure.h.  Inputs float32, every operation float64, no atomics.
 
 // One joint set of one sample, one wave: `in_set` marks the lanes whose joint belongs to the set, a member is one of them with w > 0.
 // Returns the lane's aligned error / sc (0 for a non-member and for a set left out), n = the number of members, kept = the set counts.
@@ -201,12 +241,8 @@ __global__ __launch_bounds__(64) void eval_pa_joints_kernel(const float* __restr
                                                             double* __restrict__ point_err) {
     const int b = blockIdx.x, j = threadIdx.x;
     const bool act = j < 42;
-    double p[3] = {0.0, 0.0, 0.0}, g[3] = {0.0, 0.0, 0.0}, w = 0.0;
-    if (act) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { p[k] = (double)pred[((size_t)b * 42 + j) * 3 + k]; g[k] = (double)gt[((size_t)b * 42 + j) * 4 + k]; }
-        w = (double)gt[((size_t)b * 42 + j) * 4 + 3];
-    }
+    double p[3], g[3], w;
+    load_joint(pred, gt, b, j, p, g, w);
     const double sc = scale ? (double)scale[b] : 1.0;
 #pragma nounroll
     for (int s = 0; s < 3; ++s) {
@@ -228,26 +264,18 @@ __global__ __launch_bounds__(64) void eval_pa_joints_kernel(const float* __restr
 // `part` (4,10) doubles of LDS between them.  False when var1 == 0 (the set is left out); every thread returns the same T.
 __device__ __forceinline__ bool pa_verts_transform(const float* __restrict__ P, const float* __restrict__ G, double (*part)[10],
                                                    evp_transform& T) {
-    const int tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
-    double acc[10];
+    const int tid = threadIdx.x;
+    double acc[10], sum[10];
 #pragma unroll
     for (int k = 0; k < 10; ++k) acc[k] = 0.0;
     for (int v = tid; v < NV; v += 256) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) { acc[k] += (double)P[3 * v + k]; acc[3 + k] += (double)G[3 * v + k]; }
     }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const double s = wave_reduce_sum_f64(acc[k]);
-        if (lane == 0) part[wave][k] = s;
-    }
-    __syncthreads();
+    block_sum_f64<6>(acc, part, sum);
     double m1[3], m2[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        m1[k] = (((part[0][k] + part[1][k]) + part[2][k]) + part[3][k]) / (double)NV;
-        m2[k] = (((part[0][3 + k] + part[1][3 + k]) + part[2][3 + k]) + part[3][3 + k]) / (double)NV;
-    }
+    for (int k = 0; k < 3; ++k) { m1[k] = sum[k] / (double)NV; m2[k] = sum[3 + k] / (double)NV; }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 10; ++k) acc[k] = 0.0;
@@ -261,18 +289,13 @@ __device__ __forceinline__ bool pa_verts_transform(const float* __restrict__ P, 
             for (int c = 0; c < 3; ++c) acc[3 * a + c] += x1[a] * x2[c];
         acc[9] += (x1[0] * x1[0] + x1[1] * x1[1]) + x1[2] * x1[2];
     }
-#pragma unroll
-    for (int k = 0; k < 10; ++k) {
-        const double s = wave_reduce_sum_f64(acc[k]);
-        if (lane == 0) part[wave][k] = s;
-    }
-    __syncthreads();
+    block_sum_f64<10>(acc, part, sum);
     double M[3][3];
 #pragma unroll
     for (int a = 0; a < 3; ++a)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) M[a][c] = ((part[0][3 * a + c] + part[1][3 * a + c]) + part[2][3 * a + c]) + part[3][3 * a + c];
-    const double var1 = ((part[0][9] + part[1][9]) + part[2][9]) + part[3][9];
+        for (int c = 0; c < 3; ++c) M[a][c] = sum[3 * a + c];
+    const double var1 = sum[9];
     __syncthreads();
     if (!(var1 > 0.0)) return false;
     T = procrustes_from_moments((double)NV, m1, m2, M, var1);
@@ -286,31 +309,28 @@ __global__ __launch_bounds__(256) void eval_pa_verts_kernel(const float* __restr
                                                             const float* __restrict__ params_weight, const float* __restrict__ scale,
                                                             int B, double* __restrict__ out, double* __restrict__ point_err) {
     __shared__ double part[4][10];
-    const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
+    const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
     double* o = out + ((size_t)b * 2 + h) * 2;
     double* pe = point_err ? point_err + ((size_t)b * 2 + h) * NV : nullptr;
-    const float* P = (h ? pred_l : pred_r) + (size_t)b * NV3;
-    const float* G = (h ? gt_l : gt_r) + (size_t)b * NV3;
+    const float *P, *G;
     evp_transform T;
-    const bool kept = params_weight[b * 2 + h] > 0.f && pa_verts_transform(P, G, part, T);      // uniform over the block
+    const bool kept = eval_hand(pred_r, pred_l, gt_r, gt_l, params_weight, b, h, P, G) && pa_verts_transform(P, G, part, T);      // uniform over the block
     if (!kept) {
         if (pe) for (int v = tid; v < NV; v += 256) pe[v] = 0.0;
         if (tid == 0) { o[0] = 0.0; o[1] = 0.0; }
         return;
     }
     const double sc = scale ? (double)scale[b] : 1.0;
-    double esum = 0.0;
+    double esum[1] = {0.0}, total[1];
     for (int v = tid; v < NV; v += 256) {
         const double p[3] = {(double)P[3 * v], (double)P[3 * v + 1], (double)P[3 * v + 2]};
         const double g[3] = {(double)G[3 * v], (double)G[3 * v + 1], (double)G[3 * v + 2]};
         const double e = evp_aligned_error(T, p, g) / sc;
-        esum += e;
+        esum[0] += e;
         if (pe) pe[v] = e;
     }
-    const double s = wave_reduce_sum_f64(esum);
-    if (lane == 0) part[wave][0] = s;
-    __syncthreads();
-    if (tid == 0) { o[0] = ((part[0][0] + part[1][0]) + part[2][0]) + part[3][0]; o[1] = (double)NV; }
+    block_sum_f64<1>(esum, part, total);
+    if (tid == 0) { o[0] = total[0]; o[1] = (double)NV; }
 }
 
 // ------------------------------------------------------------------------------------------ curve metrics: PCK counts, F-score counts
@@ -359,32 +379,15 @@ __global__ __launch_bounds__(64) void eval_curve_joints_kernel(const float* __re
     const bool act = j < 42;
     for (int k = j; k < T; k += 64) thr[k] = thresholds[k];
     for (int k = j; k < 3 * (EVAL_MAX_T + 1); k += 64) (&hist[0][0])[k] = 0;
-    double p[3] = {0.0, 0.0, 0.0}, g[3] = {0.0, 0.0, 0.0}, w = 0.0;
-    if (act) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { p[k] = (double)pred[((size_t)b * 42 + j) * 3 + k]; g[k] = (double)gt[((size_t)b * 42 + j) * 4 + k]; }
-        w = (double)gt[((size_t)b * 42 + j) * 4 + 3];
-    }
+    double p[3], g[3], w;
+    load_joint(pred, gt, b, j, p, g, w);
     const double sc = scale ? (double)scale[b] : 1.0;
     __syncthreads();
 
     double n[3] = {0.0, 0.0, 0.0};
     {   // ---- population 0
-        double a[3] = {p[0], p[1], p[2]}, c[3] = {g[0], g[1], g[2]};
-        bool counted = false;
-        double err = 0.0;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int root = 21 * h;
-            if (__shfl(w, root) > 0.0) {     // uniform over the wave
-#pragma unroll
-                for (int k = 0; k < 3; ++k) { a[k] -= __shfl(a[k], root); c[k] -= __shfl(c[k], root); }
-                if (act && j >= root && j < root + 21 && w > 0.0) {
-                    err = sqrt(evp_sq_dist(a[0], a[1], a[2], c[0], c[1], c[2])) / sc;
-                    counted = true;
-                }
-            }
-        }
+        double a[3] = {p[0], p[1], p[2]}, c[3] = {g[0], g[1], g[2]}, err;
+        const bool counted = root_relative_joint_error(j, w, a, c, sc, err);
         if (counted) atomicAdd(&hist[0][evp_threshold_index(err, thr, T)], 1);
         n[0] = wave_reduce_sum_f64(counted ? 1.0 : 0.0);
     }
@@ -451,12 +454,13 @@ __global__ __launch_bounds__(256) void eval_curve_verts_kernel(const float* __re
     __shared__ double part[4][10];
     __shared__ int hist[2][EVAL_MAX_T + 1];
     __shared__ int fhist[4][EVAL_MAX_F + 1];
-    const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
+    const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x, wave = tid / WAVE;
     const size_t hand = (size_t)b * 2 + h;
     double* o = counts + hand * 2 * (T + 1);
     double* fo = F > 0 ? f_counts + hand * 4 * F : nullptr;
     double* nd = nn_dist ? nn_dist + hand * 4 * NV : nullptr;
-    if (!(params_weight[b * 2 + h] > 0.f)) {         // uniform over the block
+    const float *P, *G;
+    if (!eval_hand(pred_r, pred_l, gt_r, gt_l, params_weight, b, h, P, G)) {         // uniform over the block
         for (int k = tid; k < 2 * (T + 1); k += 256) o[k] = 0.0;
         for (int k = tid; k < 4 * F; k += 256) fo[k] = 0.0;
         if (nd) for (int k = tid; k < 4 * NV; k += 256) nd[k] = 0.0;
@@ -466,30 +470,18 @@ __global__ __launch_bounds__(256) void eval_curve_verts_kernel(const float* __re
     for (int k = tid; k < F; k += 256) fthr[k] = f_thresholds[k];
     for (int k = tid; k < 2 * (EVAL_MAX_T + 1); k += 256) (&hist[0][0])[k] = 0;
     for (int k = tid; k < 4 * (EVAL_MAX_F + 1); k += 256) (&fhist[0][0])[k] = 0;
-    const float* P = (h ? pred_l : pred_r) + (size_t)b * NV3;
-    const float* G = (h ? gt_l : gt_r) + (size_t)b * NV3;
     const float* W = root_w + (size_t)h * NV;
     const double sc = scale ? (double)scale[b] : 1.0;
 
-    // ---- the two roots, float64: lane-strided partials, butterfly over the wave, waves in index order
-    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    // ---- the two roots, float64
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, root[6];
     for (int v = tid; v < NV; v += 256) {
         const double w = (double)W[v];
 #pragma unroll
         for (int k = 0; k < 3; ++k) { acc[k] += w * (double)P[3 * v + k]; acc[3 + k] += w * (double)G[3 * v + k]; }
     }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const double s = wave_reduce_sum_f64(acc[k]);
-        if (lane == 0) part[wave][k] = s;
-    }
-    __syncthreads();
-    double rootP[3], rootG[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        rootP[k] = ((part[0][k] + part[1][k]) + part[2][k]) + part[3][k];
-        rootG[k] = ((part[0][3 + k] + part[1][3 + k]) + part[2][3 + k]) + part[3][3 + k];
-    }
+    block_sum_f64<6>(acc, part, root);
+    const double rootP[3] = {root[0], root[1], root[2]}, rootG[3] = {root[3], root[4], root[5]};
     __syncthreads();
     evp_transform T_pa;
     const bool kept_pa = pa_verts_transform(P, G, part, T_pa);      // uniform over the block

@@ -34,6 +34,11 @@ import sys
 import numpy as np
 
 
+def _ratio(a, b):
+    """a / b as a float, NaN where nothing was counted (b = 0)."""
+    return float(a / b) if b > 0 else float("nan")
+
+
 def get_single_joints_error(pred, gt, joint_weights, scale_factor):
     """metric_utils.py:23-38 -- per-hand MPJPE; the root subtraction is cumulative on the same copies."""
     a, b = pred.copy(), gt.copy()
@@ -266,173 +271,155 @@ class Evaluator:
         self.image_root = image_root
         self.save_verts = True
         self.pred_results = []
-        self._device_parts = []        # (B,6) float64 device tensors + keep masks, summed lazily
-        self._device_vert_parts = []   # (B,2) float64 [sum of per-vertex errors, count]
-        self._device_pa_parts = []     # (B,4) float64 [sum of set 0, count, sum of the per-hand sets, count]
-        self._device_pa_vert_parts = []   # (B,2) float64 [sum of aligned per-vertex errors, count]
-        self._device_curve_parts = []     # (B,3,T+1) float64 counts of the joint populations
-        self._device_curve_vert_parts = []   # ((B,2,T+1) counts, (B,2,2,2,F) per-hand F counts, (B,2,2) hand counted and kept)
+        for name in self.DEVICE_ACCUMULATORS[:-1]:
+            setattr(self, name, [])
         if volume_metric:               # off: no attribute is added, a default Evaluator pickles byte for byte as before
             if volume_subdiv not in (1, 2, 4):
                 raise ValueError(f"volume_subdiv = {volume_subdiv!r}: 1, 2 or 4")
             self.volume_metric, self.volume_subdiv = True, int(volume_subdiv)
-            self._device_volume_parts = []   # (B,4) float64 [cm^3, interacting and kept, of those with count > 0, invalid]
+            self._device_volume_parts = []
+
+    # What the update_device_* methods leave on the device, one entry per batch, summed lazily.  The names and their order in __dict__
+    # are part of the pickled file; the last one exists only with volume_metric.
+    DEVICE_ACCUMULATORS = (
+        "_device_parts",              # (B,7) float64: the six words of ihmr_eval_metrics + [interacting]
+        "_device_vert_parts",         # (B,2) float64 [sum of per-vertex errors, count]
+        "_device_pa_parts",           # (B,4) float64 [sum of set 0, count, sum of the per-hand sets, count]
+        "_device_pa_vert_parts",      # (B,2) float64 [sum of aligned per-vertex errors, count]
+        "_device_curve_parts",        # (B,3,T+1) float64 counts of the joint populations
+        "_device_curve_vert_parts",   # ((B,2,T+1) counts, (B,2,2,2,F) per-hand F counts, (B,2,2) hand counted and kept)
+        "_device_volume_parts")       # (B,4) float64 [cm^3, interacting and kept, of those with count > 0, invalid]
 
     def clear(self):
-        if "_device_volume_parts" in self.__dict__:
-            self._device_volume_parts = []
         self.pred_results = []
-        self._device_parts = []
-        self._device_vert_parts = []
-        self._device_pa_parts = []
-        self._device_pa_vert_parts = []
-        self._device_curve_parts = []
-        self._device_curve_vert_parts = []
+        for name in self.DEVICE_ACCUMULATORS:
+            if name in self.__dict__ or name != "_device_volume_parts":
+                setattr(self, name, [])
+
+    def _device_rows(self, name, item=None):
+        """The parts of accumulator ``name`` (of a tuple-valued one: their entry ``item``) as one device tensor, in the order they were
+        added; None when the attribute is absent (an older pickle) or empty."""
+        parts = getattr(self, name, None)
+        if not parts:
+            return None
+        import torch
+        return torch.cat(parts if item is None else [p[item] for p in parts], dim=0)
+
+    def _add_device_sums(self, sums, name, item=None):
+        """Adds the column sums of accumulator ``name`` to ``sums`` (a view of a host vector) in place."""
+        d = self._device_column_sums(name, item)
+        if d is not None:
+            sums += d
+
+    def _device_column_sums(self, name, item=None):
+        """The column sums of :meth:`_device_rows` on the host, or None.  One reduction over all samples in the order they were added:
+        the float64 sum does not depend on how the samples were grouped into batches / launch sequences."""
+        rows = self._device_rows(name, item)
+        return None if rows is None else rows.sum(dim=0).cpu().numpy()
+
+    def _on_device(self, attr, dev, make):
+        """``make(dev)``, kept in ``self.<attr>`` and made again only for another device."""
+        cached = self.__dict__.get(attr)
+        if not isinstance(cached, tuple) or cached[0] != dev:
+            cached = (dev, make(dev))
+            setattr(self, attr, cached)
+        return cached[1]
+
+    def _root_w(self, dev, what):
+        import torch
+        assert self.root_weights is not None, f"Evaluator needs the MANO models (J_regressor) for {what}"
+        return self._on_device("_root_w_dev", dev, lambda d: torch.from_numpy(self.root_weights).to(d).contiguous())
 
     def _curve_tables(self, dev):
-        """The two threshold tables on ``dev`` (float64), uploaded once per device."""
+        """The two threshold tables on ``dev`` (float64; the second None when empty), uploaded once per device."""
         import torch
-        cached = getattr(self, "_curve_tables_dev", None)
-        if cached is None or cached[0] != dev:
-            t = torch.from_numpy(self.thresholds).to(dev)
-            f = torch.from_numpy(self.f_thresholds).to(dev) if len(self.f_thresholds) else None
-            self._curve_tables_dev = cached = (dev, t, f)
-        return cached[1], cached[2]
+        up = lambda t: torch.from_numpy(t).to(dev) if len(t) else None
+        return self._on_device("_curve_tables_dev", dev, lambda d: (up(self.thresholds), up(self.f_thresholds)))
+
+    @staticmethod
+    def _launch(entry, inputs, scale, out_shapes, args):
+        """One launch of the evaluation entry point ``entry``: ``inputs`` (and ``scale`` unless None) as float32 contiguous tensors on
+        the device of the first, one new (B, *shape) float64 tensor per ``out_shapes``; ``args(inputs, scale, B, outs)`` lays them out
+        in the entry point's order (a tensor stands for its pointer, None for NULL; the stream follows).  Returns the outputs."""
+        import torch
+
+        from . import hip
+        hip.require_gpu()
+        B, dev = inputs[0].shape[0], inputs[0].device
+        # only the pointer is read: a tensor that already is float32, contiguous and on the device is taken as it is
+        f = lambda t: t if t.dtype == torch.float32 and t.device == dev and t.is_contiguous() else t.detach().to(dev, torch.float32).contiguous()
+        ins, sc = [f(t) for t in inputs], None if scale is None else f(scale)
+        outs = [torch.empty(B, *shape, device=dev, dtype=torch.float64) for shape in out_shapes]
+        ptr = lambda a: a if a is None or isinstance(a, int) else a.data_ptr()
+        hip.check(getattr(hip.lib(), entry)(*map(ptr, args(ins, sc, B, outs)), hip.stream_ptr()), entry)
+        return outs
+
+    def _kept(self, keep, *parts):
+        """``parts`` (B,...) with the rows outside ``keep`` (B) bool set to zero -- a selection, not a product: a masked-out row may hold
+        NaN / Inf, and 0 * NaN is NaN.  The sums and counts are >= 0, so a kept row keeps its bits and a dropped one is +0."""
+        if keep is None:
+            return parts
+        import torch
+        dev = parts[0].device
+        zero = self._on_device("_zero_dev", dev, lambda d: torch.zeros((), dtype=torch.float64, device=d))
+        k = keep.to(dev, torch.bool)
+        return tuple(torch.where(k.reshape((-1,) + (1,) * (p.dim() - 1)), p, zero) for p in parts)
 
     def update_device_curves(self, pred_joints_3d, gt_joints_3d, keep=None, scale=None):
         """Counts per threshold of the three joint populations of one batch from device tensors (``ihmr_eval_curve_joints``);
         arguments as :meth:`update_device_pa`.  Accumulates lazily, see :meth:`curve_sums`."""
-        import torch
-
-        from . import hip
-        hip.require_gpu()
-        B, dev = pred_joints_3d.shape[0], pred_joints_3d.device
-        f = lambda t: t.detach().to(dev, torch.float32).contiguous()
-        p, g = f(pred_joints_3d), f(gt_joints_3d)
-        sc = None if scale is None else f(scale)
-        thr, _ = self._curve_tables(dev)
-        T = len(self.thresholds)
-        out = torch.empty(B, 3, T + 1, device=dev, dtype=torch.float64)
-        hip.check(hip.lib().ihmr_eval_curve_joints(p.data_ptr(), g.data_ptr(), None if sc is None else sc.data_ptr(), B, thr.data_ptr(), T,
-                                                   out.data_ptr(), hip.stream_ptr()), "ihmr_eval_curve_joints")
-        if keep is not None:
-            out = out * keep.to(dev, torch.float64)[:, None, None]
-        self._device_curve_parts.append(out)
+        thr, T = self._curve_tables(pred_joints_3d.device)[0], len(self.thresholds)
+        out, = self._launch("ihmr_eval_curve_joints", (pred_joints_3d, gt_joints_3d), scale, [(3, T + 1)],
+                            lambda i, sc, B, o: (*i, sc, B, thr, T, *o))
+        self._device_curve_parts.append(self._kept(keep, out)[0])
 
     def update_device_curve_verts(self, pred_right, pred_left, gt_right, gt_left, mano_params_weight, keep=None, scale=None):
         """Counts per threshold of the two vertex populations and the per-hand F-scores (raw and aligned) of one batch from device
         tensors (``ihmr_eval_curve_verts``); arguments as :meth:`update_device_verts`."""
-        import torch
-
-        from . import hip
-        hip.require_gpu()
-        assert self.root_weights is not None, "Evaluator needs the MANO models (J_regressor) for the root-relative vertex errors"
-        B, dev = pred_right.shape[0], pred_right.device
-        f = lambda t: t.detach().to(dev, torch.float32).contiguous()
-        pr, pl, gr, gl, w = f(pred_right), f(pred_left), f(gt_right), f(gt_left), f(mano_params_weight)
-        if not hasattr(self, "_root_w_dev") or self._root_w_dev.device != dev:
-            self._root_w_dev = torch.from_numpy(self.root_weights).to(dev).contiguous()
-        sc = None if scale is None else f(scale)
-        thr, fthr = self._curve_tables(dev)
+        root_w = self._root_w(pred_right.device, "the root-relative vertex errors")
+        thr, fthr = self._curve_tables(pred_right.device)
         T, F = len(self.thresholds), len(self.f_thresholds)
-        counts = torch.empty(B, 2, 2, T + 1, device=dev, dtype=torch.float64)
-        fc = torch.empty(B, 2, 2, 2, F, device=dev, dtype=torch.float64)
-        hip.check(hip.lib().ihmr_eval_curve_verts(pr.data_ptr(), pl.data_ptr(), gr.data_ptr(), gl.data_ptr(), self._root_w_dev.data_ptr(),
-                                                  w.data_ptr(), None if sc is None else sc.data_ptr(), B, thr.data_ptr(), T,
-                                                  None if fthr is None else fthr.data_ptr(), F, counts.data_ptr(),
-                                                  fc.data_ptr() if F else None, None, hip.stream_ptr()), "ihmr_eval_curve_verts")
-        # the counts stay what they are: F is formed per hand on the host (:func:`fscore_from_counts`, the one formula of both paths)
-        counted = (counts[..., T] > 0).to(torch.float64)                    # (B,2,2): hand, raw / pa
-        csum = counts[:, 0] + counts[:, 1]
-        if keep is not None:
-            k = keep.to(dev, torch.float64)
-            csum, counted = csum * k[:, None, None], counted * k[:, None, None]
+        counts, fc = self._launch("ihmr_eval_curve_verts", (pred_right, pred_left, gt_right, gt_left, mano_params_weight), scale,
+                                  [(2, 2, T + 1), (2, 2, 2, F)],
+                                  lambda i, sc, B, o: (*i[:4], root_w, i[4], sc, B, thr, T, fthr, F, o[0], o[1] if F else None, None))
+        # the counts stay what they are: F is formed per hand on the host (:func:`fscore_from_counts`, the one formula of both paths),
+        # of the hands that `counted` names -- which is why `fc` needs no selection of its own
+        counted = (counts[..., T] > 0).to(counts.dtype)                     # (B,2,2): hand, raw / pa
+        csum, counted = self._kept(keep, counts[:, 0] + counts[:, 1], counted)
         self._device_curve_vert_parts.append((csum, fc, counted))
 
     def update_device_pa(self, pred_joints_3d, gt_joints_3d, keep=None, scale=None):
         """Procrustes-aligned joint errors of one batch from device tensors (``ihmr_eval_pa_joints``): pred_joints_3d (B,42,3),
         gt_joints_3d (B,42,4); ``keep`` and ``scale`` as in :meth:`update_device`.  Accumulates lazily, see :meth:`pa_metric_sums`."""
         import torch
-
-        from . import hip
-        hip.require_gpu()
-        B, dev = pred_joints_3d.shape[0], pred_joints_3d.device
-        f = lambda t: t.detach().to(dev, torch.float32).contiguous()
-        p, g = f(pred_joints_3d), f(gt_joints_3d)
-        sc = None if scale is None else f(scale)
-        out = torch.empty(B, 3, 2, device=dev, dtype=torch.float64)
-        hip.check(hip.lib().ihmr_eval_pa_joints(p.data_ptr(), g.data_ptr(), None if sc is None else sc.data_ptr(), B, out.data_ptr(),
-                                                None, hip.stream_ptr()), "ihmr_eval_pa_joints")
-        part = torch.cat([out[:, 0], out[:, 1] + out[:, 2]], dim=1)
-        if keep is not None:
-            part = part * keep.to(dev, torch.float64)[:, None]
-        self._device_pa_parts.append(part)
+        out, = self._launch("ihmr_eval_pa_joints", (pred_joints_3d, gt_joints_3d), scale, [(3, 2)], lambda i, sc, B, o: (*i, sc, B, *o, None))
+        self._device_pa_parts.append(self._kept(keep, torch.cat([out[:, 0], out[:, 1] + out[:, 2]], dim=1))[0])
 
     def update_device_pa_verts(self, pred_right, pred_left, gt_right, gt_left, mano_params_weight, keep=None, scale=None):
         """PA-MPVPE partial sums of one batch from device tensors (``ihmr_eval_pa_verts``); arguments as :meth:`update_device_verts`."""
-        import torch
-
-        from . import hip
-        hip.require_gpu()
-        B, dev = pred_right.shape[0], pred_right.device
-        f = lambda t: t.detach().to(dev, torch.float32).contiguous()
-        pr, pl, gr, gl, w = f(pred_right), f(pred_left), f(gt_right), f(gt_left), f(mano_params_weight)
-        sc = None if scale is None else f(scale)
-        out = torch.empty(B, 2, 2, device=dev, dtype=torch.float64)
-        hip.check(hip.lib().ihmr_eval_pa_verts(pr.data_ptr(), pl.data_ptr(), gr.data_ptr(), gl.data_ptr(), w.data_ptr(),
-                                               None if sc is None else sc.data_ptr(), B, out.data_ptr(), None, hip.stream_ptr()),
-                  "ihmr_eval_pa_verts")
-        out = out[:, 0] + out[:, 1]
-        if keep is not None:
-            out = out * keep.to(dev, torch.float64)[:, None]
-        self._device_pa_vert_parts.append(out)
+        out, = self._launch("ihmr_eval_pa_verts", (pred_right, pred_left, gt_right, gt_left, mano_params_weight), scale, [(2, 2)],
+                            lambda i, sc, B, o: (*i, sc, B, *o, None))
+        self._device_pa_vert_parts.append(self._kept(keep, out[:, 0] + out[:, 1])[0])
 
     def update_device(self, pred_joints_3d, gt_joints_3d, collision_loss_origin_scale, keep=None, interacting=None, scale=None):
         """Metrics of one batch straight from device tensors: pred_joints_3d (B,42,3), gt_joints_3d (B,42,4),
         collision_loss_origin_scale (B,1556); ``keep`` (B) bool masks out padding duplicates (evaluator.py:137-146),
         ``interacting`` (B) bool = hand_type == 'interacting' (default all), ``scale`` (B) (default 1)."""
-        import ctypes as C
-
         import torch
-
-        from . import hip
-        hip.require_gpu()
-        B, dev = pred_joints_3d.shape[0], pred_joints_3d.device
-        f = lambda t: t.detach().to(dev, torch.float32).contiguous()
-        p, g, c = f(pred_joints_3d), f(gt_joints_3d), f(collision_loss_origin_scale)
-        sc = None if scale is None else f(scale)
+        dev = pred_joints_3d.device
         it = None if interacting is None else interacting.to(dev, torch.uint8).contiguous()
-        out = torch.empty(B, 6, device=dev, dtype=torch.float64)
-        hip.check(hip.lib().ihmr_eval_metrics(p.data_ptr(), g.data_ptr(), c.data_ptr(), None if sc is None else sc.data_ptr(),
-                                              None if it is None else it.data_ptr(), B, out.data_ptr(), hip.stream_ptr()), "ihmr_eval_metrics")
-        n_inter = torch.ones(B, device=dev, dtype=torch.float64) if it is None else it.to(torch.float64)
-        part = torch.cat([out, n_inter[:, None]], dim=1)      # [.., n_interacting]
-        if keep is not None:      # a selection, not a product: a masked-out row may hold NaN / Inf, and 0 * NaN is NaN
-            part = torch.where(keep.to(dev, torch.bool)[:, None], part, torch.zeros_like(part))
-        self._device_parts.append(part)
+        out, = self._launch("ihmr_eval_metrics", (pred_joints_3d, gt_joints_3d, collision_loss_origin_scale), scale, [(6,)],
+                            lambda i, sc, B, o: (*i, sc, it, B, *o))
+        n_inter = torch.ones(len(out), device=dev, dtype=torch.float64) if it is None else it.to(torch.float64)
+        self._device_parts.append(self._kept(keep, torch.cat([out, n_inter[:, None]], dim=1))[0])      # [.., n_interacting]
 
     def update_device_verts(self, pred_right, pred_left, gt_right, gt_left, mano_params_weight, keep=None, scale=None):
         """MPVPE partial sums of one batch from device tensors: the four meshes (B,778,3) and ``mano_params_weight`` (B,2)
         (a hand counts when its MANO annotation exists, i.e. weight > 0).  ``ihmr_eval_mpvpe``."""
-        import torch
-
-        from . import hip
-        hip.require_gpu()
-        assert self.root_weights is not None, "Evaluator needs the MANO models (J_regressor) for MPVPE"
-        B, dev = pred_right.shape[0], pred_right.device
-        f = lambda t: t.detach().to(dev, torch.float32).contiguous()
-        pr, pl, gr, gl, w = f(pred_right), f(pred_left), f(gt_right), f(gt_left), f(mano_params_weight)
-        if not hasattr(self, "_root_w_dev") or self._root_w_dev.device != dev:
-            self._root_w_dev = torch.from_numpy(self.root_weights).to(dev).contiguous()
-        sc = None if scale is None else f(scale)
-        out = torch.empty(B, 4, device=dev, dtype=torch.float64)
-        hip.check(hip.lib().ihmr_eval_mpvpe(pr.data_ptr(), pl.data_ptr(), gr.data_ptr(), gl.data_ptr(), self._root_w_dev.data_ptr(),
-                                            w.data_ptr(), None if sc is None else sc.data_ptr(), B, out.data_ptr(), hip.stream_ptr()),
-                  "ihmr_eval_mpvpe")
-        out = out[:, 0:2] + out[:, 2:4]
-        if keep is not None:      # a selection, as in update_device
-            out = torch.where(keep.to(dev, torch.bool)[:, None], out, torch.zeros_like(out))
-        self._device_vert_parts.append(out)
+        root_w = self._root_w(pred_right.device, "MPVPE")
+        out, = self._launch("ihmr_eval_mpvpe", (pred_right, pred_left, gt_right, gt_left, mano_params_weight), scale, [(4,)],
+                            lambda i, sc, B, o: (*i[:4], root_w, i[4], sc, B, *o))
+        self._device_vert_parts.append(self._kept(keep, out[:, 0:2] + out[:, 2:4])[0])
 
     def update_device_volume(self, pred_right, pred_left, keep=None, interacting=None):
         """Two-hand intersection volume of one batch from device tensors (``ihmr_sdf_volume`` through
@@ -465,17 +452,14 @@ class Evaluator:
         them the kernel called invalid] (float64, additive over batches and ranks): what :meth:`update_device_volume` left on the
         device.  Zeros for an Evaluator without ``volume_metric``."""
         sums = np.zeros(4, dtype=np.float64)
-        if getattr(self, "_device_volume_parts", None):
-            import torch
-            sums = sums + torch.cat(self._device_volume_parts, dim=0).sum(dim=0).cpu().numpy()
+        self._add_device_sums(sums, "_device_volume_parts")
         return sums
 
     @staticmethod
     def volume_metrics_from_sums(s):
         """``pen_volume``: mean intersection volume [cm^3] over the interacting samples; ``pen_rate``: the share of them whose hands
         intersect at all.  NaN where no sample was counted."""
-        d = lambda a, b: float(a / b) if b > 0 else float("nan")
-        return dict(pen_volume=d(s[0], s[1]), pen_rate=d(s[2], s[1]))
+        return dict(pen_volume=_ratio(s[0], s[1]), pen_rate=_ratio(s[2], s[1]))
 
     def gather_pred(self, pred_results):
         self.pred_results += pred_results
@@ -514,57 +498,54 @@ class Evaluator:
             single["j3d_error"] = get_single_joints_error(single["pred_joints_3d"], gt[:, :3], gt[:, 3:], single["scale"])
             single["pa_no_rot_inter_j3d_error"] = get_single_pa_inter_joints_error(
                 single["pred_joints_3d"], gt[:, :3], gt[:, 3:], single["scale"])
+            hands = list(self._counted_hands(pred_results, i))
             single["v3d_error"] = []
-            if "gt_right_hand_verts" in pred_results and self.root_weights is not None:   # Baseline / MLP exports
-                for h, side in enumerate(("right", "left")):
-                    if pred_results["mano_params_weight"][i][h] > 0:
-                        single["v3d_error"] += get_single_verts_error(pred_results[f"pred_{side}_hand_verts"][i],
-                                                                      pred_results[f"gt_{side}_hand_verts"][i],
-                                                                      self.root_weights[h], single["scale"])
-            if getattr(self, "pa_metrics", False):
-                p = single["pred_joints_3d"]
-                single["pa_inter_j3d_error"] = get_single_pa_error(p, gt[:, :3], gt[:, 3], single["scale"])
-                single["pa_j3d_error"] = (get_single_pa_error(p[:21], gt[:21, :3], gt[:21, 3], single["scale"])
-                                          + get_single_pa_error(p[21:], gt[21:, :3], gt[21:, 3], single["scale"]))
-                if "gt_right_hand_verts" in pred_results and self.root_weights is not None:
+            for h, pv, gv in hands:                                                        # Baseline / MLP exports
+                single["v3d_error"] += get_single_verts_error(pv, gv, self.root_weights[h], single["scale"])
+            pa, curves = getattr(self, "pa_metrics", False), getattr(self, "curve_metrics", False)
+            if curves and not pa:       # the key order of a record: the PA lists come first only where ``pa_metrics`` asks for them
+                self._add_curve_joint_list(single)
+            if pa or curves:            # the curve metrics count from the PA lists too, under the same keys
+                p, sc = single["pred_joints_3d"], single["scale"]
+                single["pa_inter_j3d_error"] = get_single_pa_error(p, gt[:, :3], gt[:, 3], sc)
+                single["pa_j3d_error"] = get_single_pa_error(p[:21], gt[:21, :3], gt[:21, 3], sc) + get_single_pa_error(p[21:], gt[21:, :3], gt[21:, 3], sc)
+                if self._exports_meshes(pred_results):
                     single["pa_v3d_error"] = []
-                    for h, side in enumerate(("right", "left")):
-                        if pred_results["mano_params_weight"][i][h] > 0:
-                            single["pa_v3d_error"] += get_single_pa_error(pred_results[f"pred_{side}_hand_verts"][i],
-                                                                          pred_results[f"gt_{side}_hand_verts"][i],
-                                                                          np.ones(len(pred_results[f"pred_{side}_hand_verts"][i])), single["scale"])
-            if getattr(self, "curve_metrics", False):
-                self._add_curve_lists(single, pred_results, i)
+                    for _, pv, gv in hands:
+                        single["pa_v3d_error"] += get_single_pa_error(pv, gv, np.ones(len(pv)), sc)
+            if curves and pa:
+                self._add_curve_joint_list(single)
+            if curves and self._exports_meshes(pred_results):
+                self._add_nn_lists(single, hands)
             if "do_flip" in pred_results and pred_results["do_flip"][i]:
                 self._flip_back_data(single)
             self.pred_results.append(single)
 
     NN_KEYS = ("nn_dist_raw_pg", "nn_dist_raw_gp", "nn_dist_pa_pg", "nn_dist_pa_gp")
 
-    def _add_curve_lists(self, single, pred_results, i):
-        """What the curve metrics are counted from: ``curve_j3d_error`` (the float64 form of ``j3d_error``, which keeps its dtype), the
-        PA lists (under the keys of ``pa_metrics``, computed whether or not that flag is set) and, where GT meshes are exported, per
-        counted hand the four nearest-neighbour distance arrays (raw / aligned, p->g / g->p)."""
+    def _exports_meshes(self, pred_results):
+        return "gt_right_hand_verts" in pred_results and self.root_weights is not None
+
+    def _counted_hands(self, pred_results, i):
+        """``(h, predicted mesh, GT mesh)`` of every hand of sample ``i`` that counts: GT meshes are exported and the hand's
+        ``mano_params_weight`` is > 0."""
+        if self._exports_meshes(pred_results):
+            for h, side in enumerate(("right", "left")):
+                if pred_results["mano_params_weight"][i][h] > 0:
+                    yield h, pred_results[f"pred_{side}_hand_verts"][i], pred_results[f"gt_{side}_hand_verts"][i]
+
+    @staticmethod
+    def _add_curve_joint_list(single):
+        """``curve_j3d_error``: the float64 form of ``j3d_error``, which keeps its dtype."""
         gt, p = single["gt_joints_3d"], single["pred_joints_3d"]
         single["curve_j3d_error"] = get_single_joints_error(np.asarray(p).astype(np.float64), np.asarray(gt[:, :3]).astype(np.float64),
                                                             gt[:, 3:], single["scale"])
-        meshes = "gt_right_hand_verts" in pred_results and self.root_weights is not None
-        if not getattr(self, "pa_metrics", False):
-            single["pa_inter_j3d_error"] = get_single_pa_error(p, gt[:, :3], gt[:, 3], single["scale"])
-            single["pa_j3d_error"] = (get_single_pa_error(p[:21], gt[:21, :3], gt[:21, 3], single["scale"])
-                                      + get_single_pa_error(p[21:], gt[21:, :3], gt[21:, 3], single["scale"]))
-            if meshes:
-                single["pa_v3d_error"] = []
-        if not meshes:
-            return
+
+    def _add_nn_lists(self, single, hands):
+        """Per counted hand the four nearest-neighbour distance arrays (raw / aligned, p->g / g->p) the F-scores are counted from."""
         for key in self.NN_KEYS:
             single[key] = []
-        for h, side in enumerate(("right", "left")):
-            if not pred_results["mano_params_weight"][i][h] > 0:
-                continue
-            pv, gv = pred_results[f"pred_{side}_hand_verts"][i], pred_results[f"gt_{side}_hand_verts"][i]
-            if not getattr(self, "pa_metrics", False):
-                single["pa_v3d_error"] += get_single_pa_error(pv, gv, np.ones(len(pv)), single["scale"])
+        for h, pv, gv in hands:
             for variant, aligned in (("raw", False), ("pa", True)):
                 r = get_single_fscore_counts(pv, gv, self.root_weights[h], single["scale"], self.f_thresholds, aligned)
                 if r is not None:
@@ -618,15 +599,8 @@ class Evaluator:
         f64 = lambda x: float(np.sum(np.asarray(x, dtype=np.float64)))
         ve = [x for p in self.pred_results for x in p.get("v3d_error", [])]
         sums = np.array([f64(e), len(e), f64(pa), len(pa), f64(ca), f64(cm), len(inter), f64(ve), len(ve)], dtype=np.float64)
-        if self._device_parts:
-            import torch
-            # one reduction over all samples in the order they were added: the float64 sum does not depend on how
-            # the samples were grouped into batches / launch sequences
-            dsum = torch.cat(self._device_parts, dim=0).sum(dim=0).cpu().numpy()
-            sums[:7] = sums[:7] + dsum
-        if self._device_vert_parts:
-            import torch
-            sums[7:9] = sums[7:9] + torch.cat(self._device_vert_parts, dim=0).sum(dim=0).cpu().numpy()
+        self._add_device_sums(sums[:7], "_device_parts")
+        self._add_device_sums(sums[7:9], "_device_vert_parts")
         return sums
 
     def pa_metric_sums(self):
@@ -636,12 +610,8 @@ class Evaluator:
         f64 = lambda x: float(np.sum(np.asarray(x, dtype=np.float64)))
         cols = [[x for p in self.pred_results for x in p.get(k, [])] for k in ("pa_inter_j3d_error", "pa_j3d_error", "pa_v3d_error")]
         sums = np.array([v for c in cols for v in (f64(c), len(c))], dtype=np.float64)
-        if getattr(self, "_device_pa_parts", None):
-            import torch
-            sums[:4] = sums[:4] + torch.cat(self._device_pa_parts, dim=0).sum(dim=0).cpu().numpy()
-        if getattr(self, "_device_pa_vert_parts", None):
-            import torch
-            sums[4:6] = sums[4:6] + torch.cat(self._device_pa_vert_parts, dim=0).sum(dim=0).cpu().numpy()
+        self._add_device_sums(sums[:4], "_device_pa_parts")
+        self._add_device_sums(sums[4:6], "_device_pa_vert_parts")
         return sums
 
     def curve_sums(self):
@@ -675,26 +645,20 @@ class Evaluator:
         cmax = [[np.max(p["collision_loss_origin_scale"].astype(np.float64)) * 1000 for p in inter]]
         cave = [[np.mean(p["collision_loss_origin_scale"].astype(np.float64)) * 1000 for p in inter]]
         n_inter = float(len(inter))
-        if getattr(self, "_device_curve_parts", None):
-            import torch
-            d = torch.cat(self._device_curve_parts, dim=0).sum(dim=0).cpu().numpy()
-            for k in range(3):
-                blocks[k] = blocks[k] + d[k]
-        if getattr(self, "_device_curve_vert_parts", None):
-            import torch
-            parts = self._device_curve_vert_parts
-            d = torch.cat([c for c, _, _ in parts], dim=0).sum(dim=0).cpu().numpy()
-            for k in range(2):
-                blocks[3 + k] = blocks[3 + k] + d[k]
-            counted = torch.cat([c for _, _, c in parts], dim=0).cpu().numpy().reshape(-1, 2)
-            fc = torch.cat([f for _, f, _ in parts], dim=0).cpu().numpy().reshape(len(counted), 2, 2, F)    # (hands, raw / pa, p->g / g->p, F)
+        d = self._device_column_sums("_device_curve_parts")
+        if d is not None:
+            blocks[:3] = [blocks[k] + d[k] for k in range(3)]
+        d = self._device_column_sums("_device_curve_vert_parts", 0)
+        if d is not None:            # the counts, then F per hand from the counts of the hands that were counted and kept
+            blocks[3:5] = [blocks[3 + k] + d[k] for k in range(2)]
+            counted = self._device_rows("_device_curve_vert_parts", 2).cpu().numpy().reshape(-1, 2)
+            fc = self._device_rows("_device_curve_vert_parts", 1).cpu().numpy().reshape(len(counted), 2, 2, F)    # (hands, raw / pa, p->g / g->p, F)
             for k, variant in enumerate(("raw", "pa")):
                 rows = fc[counted[:, k] > 0, k]
                 fvals[variant] += list(fscore_from_counts(rows[:, 0], rows[:, 1], nv))
                 hands[variant] += float(np.sum(counted[:, k] > 0))
-        if self._device_parts and getattr(self, "curve_metrics", False):
-            import torch
-            d = torch.cat(self._device_parts, dim=0)                 # columns 4, 5: mean and max depth [mm]; 6: interacting and kept
+        d = self._device_rows("_device_parts") if getattr(self, "curve_metrics", False) else None
+        if d is not None:            # columns 4, 5: mean and max depth [mm]; 6: interacting and kept
             d = d[d[:, 6] > 0].cpu().numpy()
             cave.append(d[:, 4])
             cmax.append(d[:, 5])
@@ -735,18 +699,46 @@ class Evaluator:
     def pa_metrics_from_sums(s):
         """``pa_inter_mpjpe_3d`` (one alignment over all valid joints of both hands, the reference's ``use_rot=True`` call),
         ``pa_mpjpe_3d`` (one alignment per hand) and, where aligned vertex errors were counted, ``pa_mpvpe_3d``."""
-        d = lambda a, b: float(a / b) if b > 0 else float("nan")
-        out = dict(pa_inter_mpjpe_3d=d(s[0], s[1]), pa_mpjpe_3d=d(s[2], s[3]))
+        out = dict(pa_inter_mpjpe_3d=_ratio(s[0], s[1]), pa_mpjpe_3d=_ratio(s[2], s[3]))
         if s[5] > 0:
-            out["pa_mpvpe_3d"] = d(s[4], s[5])
+            out["pa_mpvpe_3d"] = _ratio(s[4], s[5])
         return out
 
     @staticmethod
     def metrics_from_sums(s):
-        d = lambda a, b: float(a / b) if b > 0 else float("nan")
-        out = dict(mpjpe_3d=d(s[0], s[1]), inter_mpjpe_3d=d(s[2], s[3]), collision_ave=d(s[4], s[6]), collision_max=d(s[5], s[6]))
+        out = dict(mpjpe_3d=_ratio(s[0], s[1]), inter_mpjpe_3d=_ratio(s[2], s[3]), collision_ave=_ratio(s[4], s[6]), collision_max=_ratio(s[5], s[6]))
         if len(s) > 8 and s[8] > 0:        # only the models that export GT meshes (IHMR-Baseline / IHMR-MLP) have it
-            out["mpvpe_3d"] = d(s[7], s[8])
+            out["mpvpe_3d"] = _ratio(s[7], s[8])
+        return out
+
+    def _metric_families(self):
+        """The metric families this Evaluator reports, in the order of the packed vector -- base, PA, volume, curves -- each as
+        ``(its *_sums method, its *_from_sums method, the length of its sums)``."""
+        families = [(self.metric_sums, self.metrics_from_sums, 9)]
+        if getattr(self, "pa_metrics", False):
+            families.append((self.pa_metric_sums, self.pa_metrics_from_sums, 6))
+        if getattr(self, "volume_metric", False):
+            families.append((self.volume_sums, self.volume_metrics_from_sums, 4))
+        if getattr(self, "curve_metrics", False):
+            T, F, C = len(self.thresholds), len(self.f_thresholds), len(COLLISION_AUC_THRESHOLDS)
+            families.append((self.curve_sums, lambda s: self.curve_metrics_from_sums(s, self.thresholds, self.f_thresholds),
+                             5 * (T + 1) + 2 * (F + 1) + 2 * (C + 1)))
+        return families
+
+    def packed_sums(self):
+        """The sums of every family in one float64 vector: what one all-reduce carries (:func:`ihmr_amd.dist.reduce_metrics`)."""
+        parts = [sums() for sums, _, _ in self._metric_families()]
+        assert [len(p) for p in parts] == [n for _, _, n in self._metric_families()]
+        return np.concatenate(parts)
+
+    def metrics_from_packed(self, s):
+        """The metrics dict of a (reduced) :meth:`packed_sums` vector: every family's ``*_from_sums`` of its slice."""
+        families = self._metric_families()
+        assert len(s) == sum(n for _, _, n in families), (len(s), [n for _, _, n in families])
+        out, at = {}, 0
+        for _, from_sums, n in families:
+            out.update(from_sums(s[at:at + n]))
+            at += n
         return out
 
     @property

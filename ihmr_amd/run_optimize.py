@@ -131,26 +131,15 @@ def main(argv=None):
         for _, st, *_ in jobs:
             main_stream.wait_stream(st)                 # the next round's data generation reuses the instances' MANO handles
     torch.cuda.synchronize()
-    base = evaluator.metric_sums()
-    n_base = len(base)
-    # with --pa_metrics / --volume_metric / --curve_metrics all metric vectors travel in the one all-reduce
-    parts = ([base] + ([evaluator.pa_metric_sums()] if args.pa_metrics else []) + ([evaluator.volume_sums()] if args.volume_metric else [])
-             + ([evaluator.curve_sums()] if args.curve_metrics else []))
-    sums = D.reduce_metrics(np.concatenate(parts))
+    sums = D.reduce_metrics(evaluator.packed_sums())      # every metric family of this run travels in the one all-reduce
     elapsed = time.time() - t0
-    m = Evaluator.metrics_from_sums(sums[:n_base])
-    n_pa = 6 if args.pa_metrics else 0
-    n_vol = 4 if args.volume_metric else 0
-    if args.pa_metrics:
-        m.update(Evaluator.pa_metrics_from_sums(sums[n_base:n_base + n_pa]))
-    if args.volume_metric:
-        m.update(Evaluator.volume_metrics_from_sums(sums[n_base + n_pa:n_base + n_pa + n_vol]))
+    m = evaluator.metrics_from_packed(sums)
     curve_keys = ()
-    if args.curve_metrics:
-        c = Evaluator.curve_metrics_from_sums(sums[n_base + n_pa + n_vol:])
+    if args.curve_metrics:      # of the curve family the lines below carry five numbers and, in the JSON line, the three joint curves
+        c = {k: m.pop(k) for k in list(m) if k.startswith(("pck_", "auc_", "fscore_", "collision_auc_"))}
         curve_keys = ("auc_j3d", "auc_pa_inter_j3d", "auc_pa_j3d", "collision_auc_max", "collision_auc_ave")
         m.update({k: c[k] for k in curve_keys})
-        m.update({k: c[k].tolist() for k in ("pck_j3d", "pck_pa_inter_j3d", "pck_pa_j3d")})       # the curves go into the JSON line
+        m.update({k: c[k].tolist() for k in ("pck_j3d", "pck_pa_inter_j3d", "pck_pa_j3d")})
     if rank == 0:
         for k in ("mpjpe_3d", "inter_mpjpe_3d", "collision_ave", "collision_max") + (("pa_inter_mpjpe_3d", "pa_mpjpe_3d") if args.pa_metrics else ()) + (("pen_volume", "pen_rate") if args.volume_metric else ()) + curve_keys:
             print(f"{k} : {m[k]:.3f} (optimize)")

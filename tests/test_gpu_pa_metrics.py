@@ -199,6 +199,60 @@ def test_device_path_agrees_with_the_host_records(joints, verts):
     assert len(dev.metric_sums()) == 9 and not dev.metric_sums().any()      # the PA parts stay out of the nine sums
 
 
+def test_a_masked_out_row_without_finite_targets_leaves_every_pa_and_curve_sum_untouched(joints, verts):
+    """Padding duplicates are masked out by `keep`; what such a row holds must not reach a sum.  The row here passes the PA set rules
+    (a finite, spread-out prediction, weights 1) with GT coordinates of Inf: its aligned errors are NaN, and 0 * NaN is NaN -- `keep`
+    is a selection on every part of `update_device_pa`, `update_device_pa_verts`, `update_device_curves`, `update_device_curve_verts`."""
+    import torch
+
+    from ihmr_amd.evaluator import Evaluator
+    rows = np.flatnonzero(np.isfinite(joints.out).all(axis=(1, 2)) & np.isfinite(joints.pe).all(axis=(1, 2)))[:12]
+    assert len(rows) == 12
+    vrow = np.arange(12) % 3                                       # three mesh samples
+    one_hot = np.zeros(778, np.float32); one_hot[0] = 1.0
+    mano = types.SimpleNamespace(faces=np.zeros((1538, 3), np.int64), J_regressor=np.stack([one_hot] * 16))
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+    def run(jp, jg, vp, vg, vw, scale, keep):
+        ev = Evaluator(dict(right=mano, left=mano))
+        k, sc = None if keep is None else torch.from_numpy(keep), up(scale)
+        ev.update_device_pa(up(jp), up(jg), keep=k, scale=sc)
+        ev.update_device_pa_verts(up(vp[:, 0]), up(vp[:, 1]), up(vg[:, 0]), up(vg[:, 1]), up(vw), keep=k, scale=sc)
+        ev.update_device_curves(up(jp), up(jg), keep=k, scale=sc)
+        ev.update_device_curve_verts(up(vp[:, 0]), up(vp[:, 1]), up(vg[:, 0]), up(vg[:, 1]), up(vw), keep=k, scale=sc)
+        return ev
+
+    keep = np.ones(12, bool)
+    keep[4] = False
+    good = (joints.pred[rows], joints.gt[rows], verts.pred[vrow], verts.gt[vrow], verts.weight[vrow], joints.scale[rows])
+    bad_gt = np.full((1, 42, 4), np.inf, np.float32)
+    bad_gt[..., 3] = 1.0
+    bad = (joints.pred[rows[:1]], bad_gt, verts.pred[:1], np.full_like(verts.gt[:1], np.inf), np.ones((1, 2), np.float32), np.ones(1, np.float32))
+    # not vacuous: the appended row alone, unmasked, poisons the PA sums
+    alone = run(*bad, None).pa_metric_sums()
+    print("[pa] the appended row alone:", alone.tolist())
+    assert not np.isfinite(alone[0]) and not np.isfinite(alone[2]) and not np.isfinite(alone[4]) and alone[1] == 42 and alone[5] == 2 * 778
+    base = run(*good, keep)
+    masked = run(*[np.concatenate([a, b]) for a, b in zip(good, bad)], np.concatenate([keep, [False]]))
+
+    def same_plus_a_zero_row(a, b, what):
+        a, b = a.cpu().numpy(), b.cpu().numpy()
+        assert len(a) == 12 and len(b) == 13 and b[:-1].tobytes() == a.tobytes() and not b[-1].any() and np.isfinite(b).all(), what
+        assert not a[4].any() and a[0].any(), what                # the masked row of the base batch, and a kept one
+
+    for name in ("_device_pa_parts", "_device_pa_vert_parts", "_device_curve_parts"):
+        assert len(getattr(base, name)) == len(getattr(masked, name)) == 1
+        same_plus_a_zero_row(getattr(base, name)[0], getattr(masked, name)[0], name)
+    (csum_a, fc_a, counted_a), (csum_b, fc_b, counted_b) = base._device_curve_vert_parts[0], masked._device_curve_vert_parts[0]
+    same_plus_a_zero_row(csum_a, csum_b, "curve vertex counts")
+    same_plus_a_zero_row(counted_a, counted_b, "hands counted and kept")
+    # the F counts are read only for the hands that `counted` names: the kept rows are the base batch's, the last row is never read
+    assert fc_b[:-1].cpu().numpy().tobytes() == fc_a.cpu().numpy().tobytes()
+    assert masked.pa_metric_sums().tobytes() == base.pa_metric_sums().tobytes() and np.isfinite(base.pa_metric_sums()).all()
+    assert masked.curve_sums().tobytes() == base.curve_sums().tobytes() and np.isfinite(base.curve_sums()).all()
+    assert base.pa_metric_sums()[[1, 3, 5]].min() > 0 and base.curve_sums()[100] > 0
+
+
 def test_run_optimize_pa_metrics_device_and_host_agree():
     """20 samples at batch 8 (padded to 24): the PA values of the device path and of the records agree; without the flag the
     returned dict has exactly the four keys it had before the PA metrics existed, with the values the flagged run reports too."""
