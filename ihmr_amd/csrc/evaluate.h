@@ -10,6 +10,7 @@
 #pragma once
 #include "ihmr_common.h"
 #include "eval_pure.h"
+#include "contact_pure.h"
 
 // ------------------------------------------------------------------------------------------ what the kernels of this file share
 // Every sum has one fixed order (lane-strided partials, xor butterfly over the wave, waves in index order), so a sample's result does
@@ -552,5 +553,143 @@ __global__ __launch_bounds__(256) void eval_curve_verts_kernel(const float* __re
         int c = 0;
         for (int i = 0; i <= k; ++i) c += fhist[pass][i];
         fo[(size_t)pass * F + k] = (double)c;
+    }
+}
+
+// ------------------------------------------------------------------------------------------ interacting-hand metrics: MRRPE, contact consistency
+// How the two hands sit RELATIVE TO EACH OTHER, compared with the ground truth (there is no reference
+// call site).  The arithmetic and the rules are csrc/contact_pure.h.  Inputs float32, every operation float64, no float atomics, every
+// float sum in one fixed order: a sample's words do not depend on its place in the batch.
+
+// grid = ceil(B / 64), block = 64: one thread per sample.  out (B,2) doubles [e, counted]: the error of the vector from the right
+// wrist (joint 0) to the left wrist (joint 21), counted when both wrist weights are > 0 and the sample is interacting.
+__global__ __launch_bounds__(64) void eval_mrrpe_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                        const float* __restrict__ scale, const unsigned char* __restrict__ interacting,
+                                                        int B, double* __restrict__ out) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const float* P = pred + (size_t)b * 42 * 3;
+    const float* G = gt + (size_t)b * 42 * 4;
+    double p0[3], p21[3], g0[3], g21[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { p0[k] = (double)P[k]; p21[k] = (double)P[21 * 3 + k]; g0[k] = (double)G[k]; g21[k] = (double)G[21 * 4 + k]; }
+    const double sc = scale ? (double)scale[b] : 1.0;
+    double e;
+    const bool wrists = ctp_mrrpe(p0, p21, g0, g21, (double)G[3], (double)G[21 * 4 + 3], sc, e);
+    const bool counted = wrists && (interacting ? interacting[b] != 0 : true);
+    out[(size_t)b * 2] = counted ? e : 0.0;
+    out[(size_t)b * 2 + 1] = counted ? 1.0 : 0.0;
+}
+
+struct ContactLds {
+    double t[6][CTP_NV];                 // the OTHER hand: x, y, z of the predicted mesh, then of the target mesh
+    double thr[CTP_MAX_K];
+    double part[4][10];
+    int hist[3][CTP_MAX_K + 1];          // over the threshold index: in contact in both, in pred, in gt
+    int pairs;
+};
+static_assert(sizeof(ContactLds) == CTP_LDS_BYTES, "contact_pure.h names the LDS of eval_contact_kernel");
+
+// One step of the walk: target j against slot s of the thread.  The squared distance is always sq_dist(right, left).
+template <bool PAIRS>
+__device__ __forceinline__ void contact_step(const double (&qp)[3], const double (&qg)[3], const double (&t)[6], bool valid, double sc,
+                                             double tau, double limit, double& bp, double& bg, double& acc, int& npairs) {
+    const double sp = PAIRS ? evp_sq_dist(qp[0], qp[1], qp[2], t[0], t[1], t[2]) : evp_sq_dist(t[0], t[1], t[2], qp[0], qp[1], qp[2]);
+    const double sg = PAIRS ? evp_sq_dist(qg[0], qg[1], qg[2], t[3], t[4], t[5]) : evp_sq_dist(t[3], t[4], t[5], qg[0], qg[1], qg[2]);
+    bp = ctp_min_update(bp, sp);
+    bg = ctp_min_update(bg, sg);
+    if (PAIRS && valid && ctp_pair_in_contact_filtered(sg, sc, tau, limit)) {
+        acc += ctp_dist(sp, sc);
+        ++npairs;
+    }
+}
+
+// One walk over the 778 targets in LDS, j ascending.  Every lane reads the same target at the same time (a broadcast, no bank
+// conflict) and one read serves all slots; slot 3 exists for tid < 10 only, so only wave 0 walks it (`slot3` is uniform over a wave).
+template <bool PAIRS>
+__device__ __forceinline__ void contact_walk(const ContactLds& s, const double (&qp)[CTP_SLOTS][3], const double (&qg)[CTP_SLOTS][3],
+                                             bool slot3, bool valid3, double sc, double tau, double limit, double (&bp)[CTP_SLOTS],
+                                             double (&bg)[CTP_SLOTS], double (&acc)[CTP_SLOTS], int& npairs) {
+    for (int j = 0; j < NV; ++j) {
+        const double t[6] = {s.t[0][j], s.t[1][j], s.t[2][j], s.t[3][j], s.t[4][j], s.t[5][j]};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) contact_step<PAIRS>(qp[k], qg[k], t, true, sc, tau, limit, bp[k], bg[k], acc[k], npairs);
+        if (slot3) contact_step<PAIRS>(qp[3], qg[3], t, valid3, sc, tau, limit, bp[3], bg[3], acc[3], npairs);
+    }
+}
+
+// grid = (B, 2), block = 256: workgroup (b, h) owns the vertices of hand h (0 = right, 1 = left) as queries and holds the OTHER hand
+// of both mesh pairs as targets in LDS.  A sample is counted when both mano_params_weight are > 0 and use[b] != 0 (use NULL: every row).
+//   pair_out  (B,2,2)      [sum over C of d_pred, |C|] in the h = 0 row, zeros in the h = 1 row
+//   count_out (B,2,K,3)    of hand h's 778 vertices per threshold: [in contact in both, in pred, in gt]
+//   near      (B,2,2,778)  hand, pred / gt, vertex: the distance to the nearest vertex of the other hand; or NULL
+// A sample that is not counted writes zeros everywhere and does no pair work.  1 <= K <= CTP_MAX_K, thresholds ascending;
+// tau_c = thresholds[0].
+__global__ __launch_bounds__(256) void eval_contact_kernel(const float* __restrict__ pred_r, const float* __restrict__ pred_l,
+                                                           const float* __restrict__ gt_r, const float* __restrict__ gt_l,
+                                                           const float* __restrict__ params_weight, const float* __restrict__ scale,
+                                                           const unsigned char* __restrict__ use, int B,
+                                                           const double* __restrict__ thresholds, int K, double* __restrict__ pair_out,
+                                                           double* __restrict__ count_out, double* __restrict__ near) {
+    __shared__ ContactLds s;
+    const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x, wave = tid / WAVE;
+    const size_t hand = (size_t)b * 2 + h;
+    double* po = pair_out + hand * 2;
+    double* co = count_out + hand * 3 * K;
+    double* nr = near ? near + hand * 2 * NV : nullptr;
+    const bool counted = params_weight[b * 2] > 0.f && params_weight[b * 2 + 1] > 0.f && (use ? use[b] != 0 : true);   // uniform over the block
+    if (!counted) {
+        if (tid < 2) po[tid] = 0.0;
+        if (tid < 3 * K) co[tid] = 0.0;
+        if (nr) for (int k = tid; k < 2 * NV; k += 256) nr[k] = 0.0;
+        return;
+    }
+    const float* Qp = (h ? pred_l : pred_r) + (size_t)b * NV3;
+    const float* Qg = (h ? gt_l : gt_r) + (size_t)b * NV3;
+    const float* Tp = (h ? pred_r : pred_l) + (size_t)b * NV3;
+    const float* Tg = (h ? gt_r : gt_l) + (size_t)b * NV3;
+    if (tid < K) s.thr[tid] = thresholds[tid];
+    if (tid < 3 * (CTP_MAX_K + 1)) (&s.hist[0][0])[tid] = 0;
+    if (tid == 0) s.pairs = 0;
+    for (int v = tid; v < NV; v += 256) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { s.t[k][v] = (double)Tp[3 * v + k]; s.t[3 + k][v] = (double)Tg[3 * v + k]; }
+    }
+    double qp[CTP_SLOTS][3], qg[CTP_SLOTS][3], bp[CTP_SLOTS], bg[CTP_SLOTS], acc[CTP_SLOTS];
+#pragma unroll
+    for (int k = 0; k < CTP_SLOTS; ++k) {
+        const int v = tid + 256 * k;
+        bp[k] = INFINITY; bg[k] = INFINITY; acc[k] = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { qp[k][c] = v < NV ? (double)Qp[3 * v + c] : 0.0; qg[k][c] = v < NV ? (double)Qg[3 * v + c] : 0.0; }
+    }
+    const double sc = scale ? (double)scale[b] : 1.0;
+    const double tau = thresholds[0], limit = ctp_pair_limit(tau, sc);
+    int npairs = 0;
+    __syncthreads();
+    if (h == 0) contact_walk<true>(s, qp, qg, wave == 0, tid + 768 < NV, sc, tau, limit, bp, bg, acc, npairs);
+    else contact_walk<false>(s, qp, qg, wave == 0, tid + 768 < NV, sc, tau, limit, bp, bg, acc, npairs);
+#pragma unroll
+    for (int k = 0; k < CTP_SLOTS; ++k) {
+        const int v = tid + 256 * k;
+        if (v < NV) {
+            const double np = ctp_dist(bp[k], sc), ng = ctp_dist(bg[k], sc);
+            if (nr) { nr[v] = np; nr[NV + v] = ng; }
+            const int ip = ctp_contact_index(np, s.thr, K), ig = ctp_contact_index(ng, s.thr, K);
+            atomicAdd(&s.hist[0][ctp_both_index(ip, ig)], 1);
+            atomicAdd(&s.hist[1][ip], 1);
+            atomicAdd(&s.hist[2][ig], 1);
+        }
+    }
+    if (npairs) atomicAdd(&s.pairs, npairs);
+    const double mine[1] = {((acc[0] + acc[1]) + acc[2]) + acc[3]};
+    double total[1];
+    block_sum_f64<1>(mine, s.part, total);            // its barrier also orders the integer atomics above
+    if (tid == 0) { po[0] = h == 0 ? total[0] : 0.0; po[1] = h == 0 ? (double)s.pairs : 0.0; }
+    if (tid < 3 * K) {
+        const int k = tid / 3, c = tid % 3;
+        int n = 0;
+        for (int i = 0; i <= k; ++i) n += s.hist[c][i];
+        co[tid] = (double)n;
     }
 }

@@ -849,6 +849,26 @@ extern "C" int ihmr_eval_curve_verts(const float* pred_right, const float* pred_
     return (int)hipGetLastError();
 }
 
+extern "C" int ihmr_eval_mrrpe(const float* pred_joints_3d, const float* gt_joints_3d, const float* sample_scale,
+                               const unsigned char* interacting, int B, double* out, void* stream) {
+    if (!pred_joints_3d || !gt_joints_3d || !out || B < 1) return -1;
+    hipLaunchKernelGGL(eval_mrrpe_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, pred_joints_3d, gt_joints_3d, sample_scale,
+                       interacting, B, out);
+    return (int)hipGetLastError();
+}
+
+static_assert(CTP_MAX_K == IHMR_EVAL_MAX_CONTACT_THRESHOLDS, "contact_pure.h and ihmr_hip.h name one limit");
+extern "C" int ihmr_eval_contact(const float* pred_right, const float* pred_left, const float* gt_right, const float* gt_left,
+                                 const float* mano_params_weight, const float* sample_scale, const unsigned char* use, int B,
+                                 const double* thresholds, int K, double* pair_out, double* count_out, double* near, void* stream) {
+    if (!pred_right || !pred_left || !gt_right || !gt_left || !mano_params_weight || !thresholds || !pair_out || !count_out || B < 1)
+        return -1;
+    if (K < 1 || K > IHMR_EVAL_MAX_CONTACT_THRESHOLDS) return -1;
+    hipLaunchKernelGGL(eval_contact_kernel, dim3(B, 2), dim3(256), 0, (hipStream_t)stream, pred_right, pred_left, gt_right, gt_left,
+                       mano_params_weight, sample_scale, use, B, thresholds, K, pair_out, count_out, near);
+    return (int)hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------ IHMR-MLP training step
 extern "C" int ihmr_sdf_volume(const float* verts_a, const int32_t* faces_a, int n_verts_a, int n_faces_a, const float* verts_b,
                                const int32_t* faces_b, int n_verts_b, int n_faces_b, int B, int subdiv, const uint8_t* keep, float* box,

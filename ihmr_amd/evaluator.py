@@ -24,6 +24,14 @@ batches and ranks (:meth:`Evaluator.curve_sums`, :meth:`Evaluator.curve_metrics_
 common to both hands that lie inside both (``ihmr_sdf_volume``), where ``collision_ave`` / ``collision_max`` are
 depths read at vertices.  It is device-only (:meth:`Evaluator.update_device_volume`, :meth:`Evaluator.volume_sums`): no record, no
 pickled file and none of the other sums changes with it.
+
+``Evaluator(interaction_metrics=True)`` adds what compares how the two hands sit RELATIVE TO EACH OTHER with the ground truth
+(DESIGN.md section 8, row (f)7): ``mrrpe``, the error of the vector from the right wrist to the left wrist, and the contact
+consistency -- ``contact_dev`` (how far apart the predicted vertices of a vertex pair are that touches in the ground truth),
+``contact_rate`` and, per threshold of ``contact_thresholds``, the micro-averaged ``contact_precision`` / ``contact_recall`` /
+``contact_f1`` of the per-vertex contact maps.  Host records (:func:`get_single_mrrpe`, :func:`get_single_contact`) and device
+(:meth:`Evaluator.update_device_mrrpe` / :meth:`Evaluator.update_device_contact`: ``ihmr_eval_mrrpe`` / ``ihmr_eval_contact``) add up
+in :meth:`Evaluator.interaction_sums`.
 """
 from __future__ import annotations
 
@@ -238,6 +246,51 @@ def get_single_fscore_counts(pred_verts, gt_verts, root_weights, scale, f_thresh
     return np.stack([curve_counts(d_pg, f_thresholds, strict=True), curve_counts(d_gp, f_thresholds, strict=True)]), d_pg, d_gp
 
 
+# ------------------------------------------------------------------------------------------ interacting-hand metrics: MRRPE, contact
+CONTACT_THRESHOLDS = (0.003, 0.005)                 # contact thresholds in metres / scale; the first one defines the contact PAIRS
+MAX_CONTACT_THRESHOLDS = 8                          # include/ihmr_hip.h: IHMR_EVAL_MAX_CONTACT_THRESHOLDS
+
+
+def get_single_mrrpe(pred, gt, joint_weights, scale_factor):
+    """[e] with ``e = |(P[21] - P[0]) - (G[21] - G[0])| / scale`` in float64 -- the error of the vector from the right wrist to the
+    left wrist -- or [] unless the weights of both wrists are > 0.  A non-finite input gives a non-finite e, which is counted."""
+    w = np.asarray(joint_weights).reshape(-1)
+    if not (w[0] > 0 and w[21] > 0):
+        return []
+    p, g = np.asarray(pred)[:, :3].astype(np.float64), np.asarray(gt)[:, :3].astype(np.float64)
+    d = (p[21] - p[0]) - (g[21] - g[0])
+    with np.errstate(all="ignore"):
+        return [float(np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) / np.float64(scale_factor))]
+
+
+def pair_sq_distances(right, left):
+    """(778,778) float64: ``sq[i][j] = (dx*dx + dy*dy) + dz*dz`` of right[i] - left[j]."""
+    d = np.asarray(right).astype(np.float64)[:, None, :] - np.asarray(left).astype(np.float64)[None, :, :]
+    with np.errstate(all="ignore"):
+        return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+
+
+def get_single_contact(pred_r, pred_l, gt_r, gt_l, scale, thresholds):
+    """Contact consistency of ONE sample with both hands annotated: ``(pair_sum, pair_count, counts (K,3), near (2,2,778))``.
+    ``d_X(i, j) = sqrt(sq_dist(R_X[i], L_X[j])) / scale``; the contact pairs are ``C = {(i, j): d_gt(i, j) < thresholds[0]}`` (strict,
+    a NaN distance is never in contact), ``pair_sum`` the sum of ``d_pred`` over C, ``pair_count = |C|``.  ``near[h][x][v]``: the
+    distance from vertex v of hand h (0 = right) to the nearest vertex of the other hand in the predicted (x = 0) / target (x = 1)
+    pair -- the minimum on the squares, which a NaN never enters, then one root; +inf / scale without a comparable partner.
+    ``counts[k] = [tp, pp, gp]``: of the 1556 vertices those with ``near < thresholds[k]`` in both, in pred, in gt."""
+    thr, sc = np.asarray(thresholds, np.float64), np.float64(scale)
+    near = np.zeros((2, 2, len(pred_r)), np.float64)
+    with np.errstate(all="ignore"):
+        sq = [pair_sq_distances(pred_r, pred_l), pair_sq_distances(gt_r, gt_l)]
+        in_c = np.sqrt(sq[1]) / sc < thr[0]
+        d_pred = (np.sqrt(sq[0]) / sc)[in_c]
+        for x in range(2):
+            comparable = np.where(np.isnan(sq[x]), np.inf, sq[x])
+            near[0, x], near[1, x] = np.sqrt(comparable.min(axis=1)) / sc, np.sqrt(comparable.min(axis=0)) / sc
+        hit = near[None] < thr[:, None, None, None]                       # (K, hand, pred / gt, v)
+    counts = np.stack([(hit[:, :, 0] & hit[:, :, 1]).sum(axis=(1, 2)), hit[:, :, 0].sum(axis=(1, 2)), hit[:, :, 1].sum(axis=(1, 2))], axis=1)
+    return float(np.sum(d_pred)), int(in_c.sum()), counts.astype(np.float64), near
+
+
 def load_image_bgr(path):
     """The default image loader of :meth:`Evaluator.visualize_result`: (H,W,3) uint8 in BGR order, as ``cv2.imread`` returns it."""
     from PIL import Image
@@ -253,7 +306,7 @@ def write_image_bgr(path, img):
 
 class Evaluator:
     def __init__(self, mano_models=None, data_list=None, image_root="", inputSize=224, pa_metrics=False, curve_metrics=False,
-                 thresholds=None, f_thresholds=None, volume_metric=False, volume_subdiv=2):
+                 thresholds=None, f_thresholds=None, volume_metric=False, volume_subdiv=2, interaction_metrics=False, contact_thresholds=None):
         self.pa_metrics = pa_metrics    # records carry the Procrustes-aligned errors too (off: records and files as before)
         # records carry what the PCK curves, the F-scores and the collision AUC are counted from (off: records and files as before)
         self.curve_metrics = curve_metrics
@@ -278,6 +331,14 @@ class Evaluator:
                 raise ValueError(f"volume_subdiv = {volume_subdiv!r}: 1, 2 or 4")
             self.volume_metric, self.volume_subdiv = True, int(volume_subdiv)
             self._device_volume_parts = []
+        if interaction_metrics:         # off: no attribute is added either
+            self.interaction_metrics = True
+            self.contact_thresholds = check_thresholds(CONTACT_THRESHOLDS if contact_thresholds is None else contact_thresholds,
+                                                       MAX_CONTACT_THRESHOLDS, "contact_thresholds")
+            for name in self.INTERACTION_ACCUMULATORS:
+                setattr(self, name, [])
+        elif contact_thresholds is not None:
+            raise ValueError("contact_thresholds needs interaction_metrics=True")
 
     # What the update_device_* methods leave on the device, one entry per batch, summed lazily.  The names and their order in __dict__
     # are part of the pickled file; the last one exists only with volume_metric.
@@ -290,10 +351,18 @@ class Evaluator:
         "_device_curve_vert_parts",   # ((B,2,T+1) counts, (B,2,2,2,F) per-hand F counts, (B,2,2) hand counted and kept)
         "_device_volume_parts")       # (B,4) float64 [cm^3, interacting and kept, of those with count > 0, invalid]
 
+    # The same for the interacting-hand metrics; both exist only with interaction_metrics (as the volume's only with volume_metric).
+    INTERACTION_ACCUMULATORS = (
+        "_device_mrrpe_parts",        # (B,2) float64 [e, counted]
+        "_device_contact_parts")      # ((B,3) [the sample's deviation, has contact pairs, counted], (B,K,3) [tp, pp, gp] of both hands)
+
     def clear(self):
         self.pred_results = []
         for name in self.DEVICE_ACCUMULATORS:
             if name in self.__dict__ or name != "_device_volume_parts":
+                setattr(self, name, [])
+        for name in self.INTERACTION_ACCUMULATORS:
+            if name in self.__dict__:
                 setattr(self, name, [])
 
     def _device_rows(self, name, item=None):
@@ -461,6 +530,94 @@ class Evaluator:
         intersect at all.  NaN where no sample was counted."""
         return dict(pen_volume=_ratio(s[0], s[1]), pen_rate=_ratio(s[2], s[1]))
 
+    def _interaction_on(self, what):
+        if not getattr(self, "interaction_metrics", False):
+            raise RuntimeError(f"{what} needs Evaluator(interaction_metrics=True)")
+
+    def _use_mask(self, dev, *masks):
+        """The conjunction of the given (B) bool masks as uint8 on ``dev``, None when none is given."""
+        import torch
+        use = None
+        for mask in masks:
+            if mask is not None:
+                m = mask.to(dev, torch.bool)
+                use = m if use is None else use & m
+        return None if use is None else use.to(torch.uint8).contiguous()
+
+    def update_device_mrrpe(self, pred_joints_3d, gt_joints_3d, keep=None, interacting=None, scale=None):
+        """MRRPE of one batch from device tensors (``ihmr_eval_mrrpe``): pred_joints_3d (B,42,3), gt_joints_3d (B,42,4); ``keep``,
+        ``interacting`` and ``scale`` as in :meth:`update_device`.  A sample counts when both wrist weights are > 0 and it is kept and
+        interacting.  Accumulates lazily, see :meth:`interaction_sums`."""
+        self._interaction_on("update_device_mrrpe")
+        it = self._use_mask(pred_joints_3d.device, interacting)
+        out, = self._launch("ihmr_eval_mrrpe", (pred_joints_3d, gt_joints_3d), scale, [(2,)], lambda i, sc, B, o: (*i, sc, it, B, *o))
+        self._device_mrrpe_parts.append(self._kept(keep, out)[0])
+
+    def update_device_contact(self, pred_right, pred_left, gt_right, gt_left, mano_params_weight, keep=None, interacting=None, scale=None):
+        """Contact consistency of one batch from device tensors (``ihmr_eval_contact``): the four meshes (B,778,3) and
+        ``mano_params_weight`` (B,2).  A sample counts when both hands are annotated (weight > 0) and it is kept and interacting
+        (``keep``, ``interacting`` (B) bool, default all): the conjunction of the two masks is the kernel's ``use``, a row outside
+        it does no pair work and leaves zeros.  Accumulates lazily, see :meth:`interaction_sums`."""
+        import torch
+        self._interaction_on("update_device_contact")
+        dev, K = pred_right.device, len(self.contact_thresholds)
+        thr = self._on_device("_contact_table_dev", dev, lambda d: torch.from_numpy(self.contact_thresholds).to(d))
+        use = self._use_mask(dev, keep, interacting)
+        pair, counts = self._launch("ihmr_eval_contact", (pred_right, pred_left, gt_right, gt_left, mano_params_weight), scale,
+                                    [(2, 2), (2, K, 3)], lambda i, sc, B, o: (*i, sc, use, B, thr, K, o[0], o[1], None))
+        w = mano_params_weight.to(dev)
+        counted = (w[:, 0] > 0) & (w[:, 1] > 0)
+        if use is not None:
+            counted = counted & (use != 0)
+        pair = pair[:, 0] + pair[:, 1]                                         # the two hands' rows: [sum of d_pred over C, |C|]
+        has = counted & (pair[:, 1] > 0)
+        zero, one = torch.zeros_like(pair[:, 0]), torch.ones_like(pair[:, 0])
+        # the sample's deviation by a selection: 0 / 0 of a sample without contact pairs never enters a sum
+        dev_b = torch.where(has, pair[:, 0] / torch.where(has, pair[:, 1], one), zero)
+        rows = torch.stack([dev_b, torch.where(has, one, zero), torch.where(counted, one, zero)], dim=1)
+        self._device_contact_parts.append((rows, counts[:, 0] + counts[:, 1]))
+
+    def interaction_sums(self):
+        """``[sum of e, n, sum of the per-sample contact deviations, samples with contact pairs, samples counted, (tp, pp, gp) per
+        contact threshold]`` (float64, 5 + 3 K values, additive over batches and ranks): the records of an
+        ``Evaluator(interaction_metrics=True)`` whose ``hand_type`` is 'interacting' plus what :meth:`update_device_mrrpe` /
+        :meth:`update_device_contact` left on the device.  Zeros (K of the default table) for an Evaluator without the flag."""
+        K = len(getattr(self, "contact_thresholds", CONTACT_THRESHOLDS))
+        sums = np.zeros(5 + 3 * K, dtype=np.float64)
+        inter = [p for p in self.pred_results if p["hand_type"] == "interacting"]
+        e = [x for p in inter for x in p.get("mrrpe", [])]
+        sums[0], sums[1] = float(np.sum(np.asarray(e, dtype=np.float64))), len(e)
+        recs = [p for p in inter if "contact_pairs" in p]
+        devs = [p["contact_pair_sum"] / p["contact_pairs"] for p in recs if p["contact_pairs"] > 0]
+        sums[2], sums[3], sums[4] = float(np.sum(np.asarray(devs, dtype=np.float64))), len(devs), len(recs)
+        for p in recs:
+            sums[5:] += np.asarray(p["contact_counts"], np.float64).reshape(-1)
+        self._add_device_sums(sums[:2], "_device_mrrpe_parts")
+        self._add_device_sums(sums[2:5], "_device_contact_parts", 0)
+        d = self._device_column_sums("_device_contact_parts", 1)
+        if d is not None:
+            sums[5:] += d.reshape(-1)
+        return sums
+
+    @staticmethod
+    def interaction_metrics_from_sums(s, contact_thresholds=None):
+        """``mrrpe``; ``contact_dev`` (mean of the per-sample deviations over the counted samples with contact pairs), ``contact_rate``
+        (their share of the counted samples); ``contact_precision`` / ``contact_recall`` / ``contact_f1`` (K,), micro-averaged over the
+        vertices of all counted samples: P = tp / pp, R = tp / gp, F1 = 2 P R / (P + R), 0 when P + R = 0.  NaN where a denominator
+        count is 0.  The table is the one the sums were counted with (default: the Evaluator's default)."""
+        thr = check_thresholds(CONTACT_THRESHOLDS if contact_thresholds is None else contact_thresholds, MAX_CONTACT_THRESHOLDS, "contact_thresholds")
+        s = np.asarray(s, np.float64)
+        assert len(s) == 5 + 3 * len(thr), (len(s), len(thr))
+        c = s[5:].reshape(len(thr), 3)
+        nan = float("nan")
+        P = np.array([_ratio(tp, pp) for tp, pp, _ in c])
+        R = np.array([_ratio(tp, gp) for tp, _, gp in c])
+        den = P + R
+        with np.errstate(all="ignore"):
+            f1 = np.where(np.isnan(den), nan, np.where(den > 0, 2.0 * P * R / np.where(den > 0, den, 1.0), 0.0))
+        return dict(mrrpe=_ratio(s[0], s[1]), contact_dev=_ratio(s[2], s[3]), contact_rate=_ratio(s[3], s[4]),
+                    contact_precision=P, contact_recall=R, contact_f1=f1)
+
     def gather_pred(self, pred_results):
         self.pred_results += pred_results
 
@@ -517,6 +674,13 @@ class Evaluator:
                 self._add_curve_joint_list(single)
             if curves and self._exports_meshes(pred_results):
                 self._add_nn_lists(single, hands)
+            if getattr(self, "interaction_metrics", False):
+                single["mrrpe"] = get_single_mrrpe(single["pred_joints_3d"], gt[:, :3], gt[:, 3], single["scale"])
+                if all(k in pred_results for k in self.VERT_KEYS + ("mano_params_weight",)) and (np.asarray(pred_results["mano_params_weight"][i])[:2] > 0).all():
+                    m = {k: pred_results[k][i] for k in self.VERT_KEYS}
+                    s, n, counts, _ = get_single_contact(m["pred_right_hand_verts"], m["pred_left_hand_verts"], m["gt_right_hand_verts"],
+                                                         m["gt_left_hand_verts"], single["scale"], self.contact_thresholds)
+                    single["contact_pair_sum"], single["contact_pairs"], single["contact_counts"] = s, n, counts
             if "do_flip" in pred_results and pred_results["do_flip"][i]:
                 self._flip_back_data(single)
             self.pred_results.append(single)
@@ -712,7 +876,7 @@ class Evaluator:
         return out
 
     def _metric_families(self):
-        """The metric families this Evaluator reports, in the order of the packed vector -- base, PA, volume, curves -- each as
+        """The metric families this Evaluator reports, in the order of the packed vector -- base, PA, volume, curves, interaction -- each as
         ``(its *_sums method, its *_from_sums method, the length of its sums)``."""
         families = [(self.metric_sums, self.metrics_from_sums, 9)]
         if getattr(self, "pa_metrics", False):
@@ -723,6 +887,9 @@ class Evaluator:
             T, F, C = len(self.thresholds), len(self.f_thresholds), len(COLLISION_AUC_THRESHOLDS)
             families.append((self.curve_sums, lambda s: self.curve_metrics_from_sums(s, self.thresholds, self.f_thresholds),
                              5 * (T + 1) + 2 * (F + 1) + 2 * (C + 1)))
+        if getattr(self, "interaction_metrics", False):      # the last family: the slices of the others do not move
+            families.append((self.interaction_sums, lambda s: self.interaction_metrics_from_sums(s, self.contact_thresholds),
+                             5 + 3 * len(self.contact_thresholds)))
         return families
 
     def packed_sums(self):

@@ -49,6 +49,11 @@ def main(argv=None):
                     help="also report pen_volume (mean two-hand intersection volume in cm^3 over the interacting samples) and pen_rate "
                          "(the share of them whose hands intersect): counted on the device (ihmr_sdf_volume); there is no host path, "
                          "so not together with --host_eval")
+    ap.add_argument("--mrrpe", action="store_true",
+                    help="also report mrrpe, the mean relative-root position error (the error of the vector from the right wrist to "
+                         "the left wrist, over the interacting samples with both wrists valid): on the device (ihmr_eval_mrrpe), from "
+                         "the records under --host_eval.  IHMR-OPT exports no GT meshes: the contact-consistency part of the "
+                         "interacting-hand metrics (Evaluator.update_device_contact) has nothing to compare with here")
     ap.add_argument("--volume_subdiv", type=int, default=2, choices=[1, 2, 4], help="the volume grid is (32 * volume_subdiv)^3")
     ap.add_argument("--streams", type=int, default=1,
                     help="model instances driven side by side on their own HIP streams (2 x --fuse_batches 8 saturates one MI355X; "
@@ -74,7 +79,7 @@ def main(argv=None):
     main_stream = torch.cuda.current_stream()
     streams = [torch.cuda.Stream() for _ in range(S)] if S > 1 else [main_stream]
     evaluator = Evaluator(model.mano_models, pa_metrics=args.pa_metrics, curve_metrics=args.curve_metrics,
-                          volume_metric=args.volume_metric, volume_subdiv=args.volume_subdiv)
+                          volume_metric=args.volume_metric, volume_subdiv=args.volume_subdiv, interaction_metrics=args.mrrpe)
     fwd = lambda p, s, t: two_hand.forward_from_packed(model.mano_models["right"], p.cuda(), s.cuda(), t.cuda())[2]
 
     idx, is_pad = D.shard_indices(args.num_samples, args.batchSize, rank, world)
@@ -126,6 +131,8 @@ def main(argv=None):
                         evaluator.update_device_pa(mdl.pred_joints_3d, mdl.buf["gt_joints_3d"], keep=torch.from_numpy(~pad))
                     if args.curve_metrics:
                         evaluator.update_device_curves(mdl.pred_joints_3d, mdl.buf["gt_joints_3d"], keep=torch.from_numpy(~pad))
+                    if args.mrrpe:
+                        evaluator.update_device_mrrpe(mdl.pred_joints_3d, mdl.buf["gt_joints_3d"], keep=torch.from_numpy(~pad))
                     if args.volume_metric:
                         evaluator.update_device_volume(mdl.pred_right_hand_verts, mdl.pred_left_hand_verts, keep=torch.from_numpy(~pad))
         for _, st, *_ in jobs:
@@ -140,8 +147,11 @@ def main(argv=None):
         curve_keys = ("auc_j3d", "auc_pa_inter_j3d", "auc_pa_j3d", "collision_auc_max", "collision_auc_ave")
         m.update({k: c[k] for k in curve_keys})
         m.update({k: c[k].tolist() for k in ("pck_j3d", "pck_pa_inter_j3d", "pck_pa_j3d")})
+    if args.mrrpe:              # of the interaction family the line carries mrrpe: there are no GT meshes to count contact against
+        for k in [k for k in m if k.startswith("contact_")]:
+            m.pop(k)
     if rank == 0:
-        for k in ("mpjpe_3d", "inter_mpjpe_3d", "collision_ave", "collision_max") + (("pa_inter_mpjpe_3d", "pa_mpjpe_3d") if args.pa_metrics else ()) + (("pen_volume", "pen_rate") if args.volume_metric else ()) + curve_keys:
+        for k in ("mpjpe_3d", "inter_mpjpe_3d", "collision_ave", "collision_max") + (("pa_inter_mpjpe_3d", "pa_mpjpe_3d") if args.pa_metrics else ()) + (("pen_volume", "pen_rate") if args.volume_metric else ()) + (("mrrpe",) if args.mrrpe else ()) + curve_keys:
             print(f"{k} : {m[k]:.3f} (optimize)")
         print(json.dumps(dict(num_samples=args.num_samples, world=world, seconds=elapsed, **m)))
     if torch.distributed.is_available() and torch.distributed.is_initialized():

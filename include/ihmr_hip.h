@@ -351,6 +351,36 @@ int ihmr_eval_curve_verts(const float* pred_right, const float* pred_left, const
                           const double* thresholds, int T, const double* f_thresholds, int F, double* counts, double* f_counts,
                           double* nn_dist, void* stream);
 
+/* Interacting-hand metrics: how the two hands sit RELATIVE TO EACH OTHER, compared with the ground truth.  The definitions are
+ * decisions of this build, DESIGN.md section 8 row (f)7 (there is no reference call site); csrc/contact_pure.h states the arithmetic.
+ * Float64 arithmetic on the float32 inputs, every squared distance (dx*dx + dy*dy) + dz*dz, one root per distance, every distance
+ * divided by sample_scale (B) or NULL (= 1) before it is compared or summed.
+ *   ihmr_eval_mrrpe    mean relative-root position error: e = |(P[21] - P[0]) - (G[21] - G[0])| / scale of pred_joints_3d (B,42,3) and
+ *                      gt_joints_3d (B,42,4) [xyz, weight], counted when the weights of both wrists (joints 0 and 21) are > 0 and
+ *                      interacting[b] != 0 (interacting (B) bytes or NULL = all).  out (B,2) float64 [e, counted]; [0, 0] otherwise.  A
+ *                      non-finite input gives a non-finite e, which is counted.
+ *   ihmr_eval_contact  the four meshes (B,778,3).  A sample is counted when both mano_params_weight (B,2) are > 0 and use[b] != 0
+ *                      (use (B) bytes or NULL = all); a row outside `use` does no pair work.  thresholds (K): a DEVICE pointer to a
+ *                      float64 table, caller-owned, finite and strictly ascending; tau_c = thresholds[0].
+ *                      d_X(i, j) = sqrt(sq_dist(right_X[i], left_X[j])) / scale for X in {pred, gt}; C = {(i, j): d_gt(i, j) < tau_c}
+ *                      (strict; a NaN distance is never in contact).
+ *                      pair_out  (B,2,2)      hand row 0: [sum over C of d_pred, |C|]; hand row 1: zeros (the caller adds the rows)
+ *                      count_out (B,2,K,3)    hand (right, left), tau_k: of the hand's 778 vertices the number in contact
+ *                                             [in pred and gt, in pred, in gt]; a vertex is in contact in X when near_X < tau_k (strict)
+ *                      near      (B,2,2,778)  or NULL: hand, pred / gt, vertex: the distance to the nearest vertex of the OTHER hand,
+ *                                             the minimum taken on the squares, one root; a NaN never replaces the running minimum, a
+ *                                             vertex without a comparable partner has sqrt(+inf) / scale.
+ *                      A sample that is not counted writes zeros everywhere.  The float64 pair sum has one fixed order: a sample's
+ *                      words do not depend on its place in the batch.
+ * -1, nothing launched: a NULL required pointer, B < 1, K < 1, K > IHMR_EVAL_MAX_CONTACT_THRESHOLDS.  No allocation, no
+ * synchronisation. */
+#define IHMR_EVAL_MAX_CONTACT_THRESHOLDS 8
+int ihmr_eval_mrrpe(const float* pred_joints_3d, const float* gt_joints_3d, const float* sample_scale, const unsigned char* interacting,
+                    int B, double* out, void* stream);
+int ihmr_eval_contact(const float* pred_right, const float* pred_left, const float* gt_right, const float* gt_left,
+                      const float* mano_params_weight, const float* sample_scale, const unsigned char* use, int B,
+                      const double* thresholds, int K, double* pair_out, double* count_out, double* near, void* stream);
+
 /* ------------------------------------------------------------------ two-hand intersection volume
  * How much of one mesh lies inside the other, counted in voxels of ONE grid common to both (csrc/volume_pure.h states the arithmetic
  * down to the float operation).  Per sample two CLOSED triangle meshes A and B: verts (B,n_verts,3) float32, one
