@@ -22,6 +22,7 @@
 #include "encoder_bf16.h"
 #include "evaluate.h"
 #include "volume.h"
+#include "surface.h"
 #include "train.h"
 #include "train_conv.h"
 #include "copy_pack.h"
@@ -875,6 +876,18 @@ extern "C" int ihmr_sdf_volume(const float* verts_a, const int32_t* faces_a, int
                                int32_t* status, uint32_t* counts, uint32_t* bits, void* stream) {
     return vol_launch(verts_a, faces_a, n_verts_a, n_faces_a, verts_b, faces_b, n_verts_b, n_faces_b, B, subdiv, keep, box, status,
                       counts, bits, (hipStream_t)stream);
+}
+
+extern "C" int ihmr_surface_distance(const float* points, int P, const float* verts, int V, const int32_t* faces, int F_dist, int F_total,
+                                     const uint8_t* use, int B, int is_signed, double* dist, int32_t* face, double* bary, void* stream) {
+    return srf_launch(points, P, verts, V, faces, F_dist, F_total, use, B, is_signed, dist, face, bary, (hipStream_t)stream);
+}
+
+extern "C" int ihmr_surface_distance_bwd(const float* points, int P, const float* verts, int V, const int32_t* faces, int F_dist,
+                                         int F_total, const uint8_t* use, int B, const double* dist, const int32_t* face,
+                                         const double* bary, const double* g_dist, float* d_points, float* d_verts, void* stream) {
+    return srf_launch_bwd(points, P, verts, V, faces, F_dist, F_total, use, B, dist, face, bary, g_dist, d_points, d_verts,
+                          (hipStream_t)stream);
 }
 
 extern "C" int ihmr_mlp_train_grad(const ihmr_mano* m, const ihmr_mano* m_left, const ihmr_opt_io* io, int B,

@@ -32,6 +32,13 @@ consistency -- ``contact_dev`` (how far apart the predicted vertices of a vertex
 ``contact_f1`` of the per-vertex contact maps.  Host records (:func:`get_single_mrrpe`, :func:`get_single_contact`) and device
 (:meth:`Evaluator.update_device_mrrpe` / :meth:`Evaluator.update_device_contact`: ``ihmr_eval_mrrpe`` / ``ihmr_eval_contact``) add up
 in :meth:`Evaluator.interaction_sums`.
+
+``Evaluator(surface_metrics=True)`` measures against the SURFACE of the other hand (``ihmr_surface_distance``, DESIGN.md section 8, row
+(f)8): ``pen_depth_max`` / ``pen_depth_ave`` / ``pen_vertex_rate`` -- the depth of a vertex under the other hand's skin in true
+millimetres, the exact counterparts of ``collision_max`` / ``collision_ave`` -- and, with GT meshes, ``surface_contact_precision`` /
+``surface_contact_recall`` / ``surface_contact_f1`` per threshold of ``surface_thresholds``, where a vertex is in contact when its
+distance to the other hand's surface (not to its nearest vertex) lies below the threshold.  Device-only, like the volume
+(:meth:`Evaluator.update_device_surface`, :meth:`Evaluator.surface_sums`).
 """
 from __future__ import annotations
 
@@ -249,6 +256,7 @@ def get_single_fscore_counts(pred_verts, gt_verts, root_weights, scale, f_thresh
 # ------------------------------------------------------------------------------------------ interacting-hand metrics: MRRPE, contact
 CONTACT_THRESHOLDS = (0.003, 0.005)                 # contact thresholds in metres / scale; the first one defines the contact PAIRS
 MAX_CONTACT_THRESHOLDS = 8                          # include/ihmr_hip.h: IHMR_EVAL_MAX_CONTACT_THRESHOLDS
+SURFACE_THRESHOLDS = (0.003, 0.005)                 # surface-contact thresholds in metres / scale (at most MAX_CONTACT_THRESHOLDS)
 
 
 def get_single_mrrpe(pred, gt, joint_weights, scale_factor):
@@ -306,7 +314,8 @@ def write_image_bgr(path, img):
 
 class Evaluator:
     def __init__(self, mano_models=None, data_list=None, image_root="", inputSize=224, pa_metrics=False, curve_metrics=False,
-                 thresholds=None, f_thresholds=None, volume_metric=False, volume_subdiv=2, interaction_metrics=False, contact_thresholds=None):
+                 thresholds=None, f_thresholds=None, volume_metric=False, volume_subdiv=2, interaction_metrics=False, contact_thresholds=None,
+                 surface_metrics=False, surface_thresholds=None):
         self.pa_metrics = pa_metrics    # records carry the Procrustes-aligned errors too (off: records and files as before)
         # records carry what the PCK curves, the F-scores and the collision AUC are counted from (off: records and files as before)
         self.curve_metrics = curve_metrics
@@ -339,6 +348,14 @@ class Evaluator:
                 setattr(self, name, [])
         elif contact_thresholds is not None:
             raise ValueError("contact_thresholds needs interaction_metrics=True")
+        if surface_metrics:             # off: no attribute is added either
+            self.surface_metrics = True
+            self.surface_thresholds = check_thresholds(SURFACE_THRESHOLDS if surface_thresholds is None else surface_thresholds,
+                                                       MAX_CONTACT_THRESHOLDS, "surface_thresholds")
+            for name in self.SURFACE_ACCUMULATORS:
+                setattr(self, name, [])
+        elif surface_thresholds is not None:
+            raise ValueError("surface_thresholds needs surface_metrics=True")
 
     # What the update_device_* methods leave on the device, one entry per batch, summed lazily.  The names and their order in __dict__
     # are part of the pickled file; the last one exists only with volume_metric.
@@ -356,12 +373,16 @@ class Evaluator:
         "_device_mrrpe_parts",        # (B,2) float64 [e, counted]
         "_device_contact_parts")      # ((B,3) [the sample's deviation, has contact pairs, counted], (B,K,3) [tp, pp, gp] of both hands)
 
+    # The same for the surface metrics; it exists only with surface_metrics.
+    SURFACE_ACCUMULATORS = (
+        "_device_surface_parts",)     # ((B,5) [max depth mm, mean depth mm, inside vertices, counted, counted with GT], (B,K,3) [tp, pp, gp])
+
     def clear(self):
         self.pred_results = []
         for name in self.DEVICE_ACCUMULATORS:
             if name in self.__dict__ or name != "_device_volume_parts":
                 setattr(self, name, [])
-        for name in self.INTERACTION_ACCUMULATORS:
+        for name in self.INTERACTION_ACCUMULATORS + self.SURFACE_ACCUMULATORS:
             if name in self.__dict__:
                 setattr(self, name, [])
 
@@ -617,6 +638,90 @@ class Evaluator:
             f1 = np.where(np.isnan(den), nan, np.where(den > 0, 2.0 * P * R / np.where(den > 0, den, 1.0), 0.0))
         return dict(mrrpe=_ratio(s[0], s[1]), contact_dev=_ratio(s[2], s[3]), contact_rate=_ratio(s[3], s[4]),
                     contact_precision=P, contact_recall=R, contact_f1=f1)
+
+    def update_device_surface(self, pred_right, pred_left, gt_right=None, gt_left=None, mano_params_weight=None, scale=None, keep=None,
+                              interacting=None):
+        """Penetration depth and surface contact of one batch from device tensors (``ihmr_surface_distance`` through
+        :func:`ihmr_amd.sdf.surface_distance`, ``Evaluator(surface_metrics=True)``): per mesh pair two calls, each hand's 778 vertices
+        against the other hand's mesh with the wrist closed.  ``keep`` and ``interacting`` (B) bool, default all: their conjunction is
+        the kernel's ``use``, a sample outside it does no work and counts nowhere.  ``scale`` (B), default 1: every distance is divided
+        by it.  ``depth = max(0, -dist) / scale``; a sample leaves the maximum and the mean of its 1556 depths in millimetres and the
+        number of its vertices with ``dist < 0``.  With the GT meshes and ``mano_params_weight`` (B,2), a sample whose two weights are > 0
+        also leaves, per threshold, the vertices in contact (``dist / scale < tau``, strict; inside is contact) in both mesh pairs, in
+        the prediction and in the ground truth.  Accumulates lazily, see :meth:`surface_sums`.  Device-only: the records,
+        every other ``*_sums()`` and pickled files carry nothing of it."""
+        import torch
+
+        from . import hip, sdf
+        if not getattr(self, "surface_metrics", False):
+            raise RuntimeError("update_device_surface needs Evaluator(surface_metrics=True)")
+        hip.require_gpu()
+        assert self.right_hand_faces is not None and self.left_hand_faces is not None, "Evaluator needs the MANO models' faces"
+        if (gt_right is None) != (gt_left is None) or (gt_right is not None and mano_params_weight is None):
+            raise ValueError("the contact part needs gt_right, gt_left and mano_params_weight together")
+        B, dev, K = pred_right.shape[0], pred_right.device, len(self.surface_thresholds)
+        use = torch.ones(B, dtype=torch.bool, device=dev)
+        for mask in (keep, interacting):
+            if mask is not None:
+                use = use & mask.to(dev, torch.bool)
+        sc = torch.ones(B, dtype=torch.float64, device=dev) if scale is None else scale.detach().to(dev, torch.float32).to(torch.float64)
+
+        def both_hands(right, left, rows):
+            d_r = sdf.surface_distance(right.detach(), left.detach(), self.left_hand_faces, use=rows)[0]
+            d_l = sdf.surface_distance(left.detach(), right.detach(), self.right_hand_faces, use=rows)[0]
+            return torch.cat([d_r, d_l], dim=1)                                  # (B,1556): a row outside `rows` is zero
+
+        zero = self._on_device("_zero_dev", dev, lambda d: torch.zeros((), dtype=torch.float64, device=d))
+        dp = both_hands(pred_right, pred_left, use)
+        depth = torch.where(dp < 0, -dp, zero) / sc[:, None]                    # a NaN distance (a NaN vertex) has depth 0
+        n = use.to(torch.float64)
+        inside = ((dp < 0) & use[:, None]).sum(dim=1).to(torch.float64)
+        rows = [torch.where(use, depth.max(dim=1).values * 1000.0, zero), torch.where(use, depth.mean(dim=1) * 1000.0, zero), inside, n]
+        counts = torch.zeros(B, K, 3, dtype=torch.float64, device=dev)
+        with_gt = torch.zeros_like(n)
+        if gt_right is not None:
+            w = mano_params_weight.to(dev)
+            counted = use & (w[:, 0] > 0) & (w[:, 1] > 0)
+            dg = both_hands(gt_right, gt_left, counted)
+            thr = self._on_device("_surface_table_dev", dev, lambda d: torch.from_numpy(self.surface_thresholds).to(d))
+            live = counted[:, None, None]
+            in_p = ((dp / sc[:, None])[:, None, :] < thr[None, :, None]) & live           # (B,K,1556)
+            in_g = ((dg / sc[:, None])[:, None, :] < thr[None, :, None]) & live
+            counts = torch.stack([(in_p & in_g).sum(dim=2), in_p.sum(dim=2), in_g.sum(dim=2)], dim=2).to(torch.float64)
+            with_gt = counted.to(torch.float64)
+        self._device_surface_parts.append((torch.stack(rows + [with_gt], dim=1), counts))
+
+    def surface_sums(self):
+        """``[sum of the per-sample maximum depths, sum of the per-sample mean depths (mm), vertices inside the other hand, samples
+        counted, samples counted with GT meshes, (tp, pp, gp) per surface threshold]`` (float64, 5 + 3 K values, additive over batches
+        and ranks): what :meth:`update_device_surface` left on the device.  Zeros (K of the default table) for an Evaluator without
+        ``surface_metrics``."""
+        K = len(getattr(self, "surface_thresholds", SURFACE_THRESHOLDS))
+        sums = np.zeros(5 + 3 * K, dtype=np.float64)
+        self._add_device_sums(sums[:5], "_device_surface_parts", 0)
+        d = self._device_column_sums("_device_surface_parts", 1)
+        if d is not None:
+            sums[5:] += d.reshape(-1)
+        return sums
+
+    @staticmethod
+    def surface_metrics_from_sums(s, surface_thresholds=None):
+        """``pen_depth_max`` / ``pen_depth_ave``: the mean over the counted samples of the maximum / mean depth of the 1556 vertices
+        under the other hand's surface [mm]; ``pen_vertex_rate``: the share of their vertices that lie inside the other hand;
+        ``surface_contact_precision`` / ``surface_contact_recall`` / ``surface_contact_f1`` (K,), micro-averaged over the vertices of the
+        samples counted with GT meshes exactly as ``contact_*``.  NaN where a denominator is 0."""
+        thr = check_thresholds(SURFACE_THRESHOLDS if surface_thresholds is None else surface_thresholds, MAX_CONTACT_THRESHOLDS, "surface_thresholds")
+        s = np.asarray(s, np.float64)
+        assert len(s) == 5 + 3 * len(thr), (len(s), len(thr))
+        c = s[5:].reshape(len(thr), 3)
+        nan = float("nan")
+        P = np.array([_ratio(tp, pp) for tp, pp, _ in c])
+        R = np.array([_ratio(tp, gp) for tp, _, gp in c])
+        den = P + R
+        with np.errstate(all="ignore"):
+            f1 = np.where(np.isnan(den), nan, np.where(den > 0, 2.0 * P * R / np.where(den > 0, den, 1.0), 0.0))
+        return dict(pen_depth_max=_ratio(s[0], s[3]), pen_depth_ave=_ratio(s[1], s[3]), pen_vertex_rate=_ratio(s[2], 1556.0 * s[3]),
+                    surface_contact_precision=P, surface_contact_recall=R, surface_contact_f1=f1)
 
     def gather_pred(self, pred_results):
         self.pred_results += pred_results
@@ -876,7 +981,7 @@ class Evaluator:
         return out
 
     def _metric_families(self):
-        """The metric families this Evaluator reports, in the order of the packed vector -- base, PA, volume, curves, interaction -- each as
+        """The metric families this Evaluator reports, in the order of the packed vector -- base, PA, volume, curves, interaction, surface -- each as
         ``(its *_sums method, its *_from_sums method, the length of its sums)``."""
         families = [(self.metric_sums, self.metrics_from_sums, 9)]
         if getattr(self, "pa_metrics", False):
@@ -890,6 +995,9 @@ class Evaluator:
         if getattr(self, "interaction_metrics", False):      # the last family: the slices of the others do not move
             families.append((self.interaction_sums, lambda s: self.interaction_metrics_from_sums(s, self.contact_thresholds),
                              5 + 3 * len(self.contact_thresholds)))
+        if getattr(self, "surface_metrics", False):          # appended after the interaction family: no existing slice moves
+            families.append((self.surface_sums, lambda s: self.surface_metrics_from_sums(s, self.surface_thresholds),
+                             5 + 3 * len(self.surface_thresholds)))
         return families
 
     def packed_sums(self):

@@ -24,6 +24,7 @@ NUM_VERTS, NUM_FACES, NUM_JOINTS, OPT_NPARAM = 778, 1538, 16, 122
 EVAL_MAX_THRESHOLDS, EVAL_MAX_F_THRESHOLDS = 256, 8      # include/ihmr_hip.h: IHMR_EVAL_MAX_THRESHOLDS, IHMR_EVAL_MAX_F_THRESHOLDS
 EVAL_MAX_CONTACT_THRESHOLDS = 8                          # include/ihmr_hip.h: IHMR_EVAL_MAX_CONTACT_THRESHOLDS
 VOLUME_MAX_VERTS, VOLUME_MAX_FACES = 1024, 2048          # include/ihmr_hip.h: IHMR_VOLUME_MAX_VERTS, IHMR_VOLUME_MAX_FACES
+SURFACE_MAX_VERTS, SURFACE_MAX_FACES = 1024, 2048        # include/ihmr_hip.h: IHMR_SURFACE_MAX_VERTS, IHMR_SURFACE_MAX_FACES
 # include/ihmr_hip.h: parameter blocks (slot order of the 122-vector), filter / select losses, optimizers
 PARAM_BLOCKS = dict(pred_cam_params=(1, 0, 3), pred_hand_trans=(2, 3, 3), pred_right_orient=(4, 6, 3), pred_left_orient=(8, 9, 3),
                     pred_right_pose_params=(16, 12, 45), pred_left_pose_params=(32, 57, 45),
@@ -38,7 +39,7 @@ EXPORTED_SYMBOLS = [
     "ihmr_sdf_workspace_bytes", "ihmr_sdf_collision", "ihmr_sdf_collision_ex", "ihmr_sdf_dense_grid", "ihmr_opt_workspace_bytes",
     "ihmr_opt_run_stage", "ihmr_opt_forward_losses", "ihmr_opt_sdf_stats", "ihmr_opt_sdf_counters", "ihmr_opt_sdf_inside_bits", "ihmr_opt_stage_graph_create",
     "ihmr_opt_forward_graph_create", "ihmr_graph_launch", "ihmr_graph_destroy", "ihmr_opt_set_params", "ihmr_eval_metrics", "ihmr_eval_mpvpe", "ihmr_eval_pa_joints", "ihmr_eval_pa_verts",
-    "ihmr_eval_curve_joints", "ihmr_eval_curve_verts", "ihmr_eval_mrrpe", "ihmr_eval_contact", "ihmr_sdf_volume", "ihmr_conv_igemm", "ihmr_maxpool3x3s2",
+    "ihmr_eval_curve_joints", "ihmr_eval_curve_verts", "ihmr_eval_mrrpe", "ihmr_eval_contact", "ihmr_sdf_volume", "ihmr_surface_distance", "ihmr_surface_distance_bwd", "ihmr_conv_igemm", "ihmr_maxpool3x3s2",
     "ihmr_avgpool_relu", "ihmr_preprocess_images", "ihmr_mlp_train_grad", "ihmr_transpose", "ihmr_relu_backward", "ihmr_colsum",
     "ihmr_adam_step", "ihmr_bn_workspace_bytes", "ihmr_bn_train_forward", "ihmr_bn_train_backward", "ihmr_conv_wgrad",
     "ihmr_dilate2", "ihmr_interleave2", "ihmr_pack_dgrad_weight", "ihmr_maxpool3x3s2_backward", "ihmr_avgpool_relu_backward", "ihmr_set_kernel_timer", "ihmr_flush_kernel_timer",
@@ -291,7 +292,9 @@ def lib():
                           ("ihmr_eval_curve_verts", [vp] * 7 + [i, vp, i, vp, i, vp, vp, vp, vp]),
                           ("ihmr_eval_mrrpe", [vp, vp, vp, vp, i, vp, vp]),
                           ("ihmr_eval_contact", [vp] * 7 + [i, vp, i, vp, vp, vp, vp]),
-                          ("ihmr_sdf_volume", [vp, vp, i, i, vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp])):
+                          ("ihmr_sdf_volume", [vp, vp, i, i, vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp]),
+                          ("ihmr_surface_distance", [vp, i, vp, i, vp, i, i, vp, i, i, vp, vp, vp, vp]),
+                          ("ihmr_surface_distance_bwd", [vp, i, vp, i, vp, i, i, vp, i, vp, vp, vp, vp, vp, vp, vp])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = sig
         L.ihmr_graph_destroy.argtypes = [vp]

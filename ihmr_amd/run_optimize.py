@@ -54,6 +54,11 @@ def main(argv=None):
                          "the left wrist, over the interacting samples with both wrists valid): on the device (ihmr_eval_mrrpe), from "
                          "the records under --host_eval.  IHMR-OPT exports no GT meshes: the contact-consistency part of the "
                          "interacting-hand metrics (Evaluator.update_device_contact) has nothing to compare with here")
+    ap.add_argument("--surface_metrics", action="store_true",
+                    help="also report pen_depth_max / pen_depth_ave (the depth of the vertices under the OTHER hand's surface in true "
+                         "millimetres, the exact counterparts of collision_max / collision_ave) and pen_vertex_rate (the share of "
+                         "vertices inside the other hand): on the device (ihmr_surface_distance); there is no host path, so not "
+                         "together with --host_eval.  IHMR-OPT exports no GT meshes: no surface-contact part")
     ap.add_argument("--volume_subdiv", type=int, default=2, choices=[1, 2, 4], help="the volume grid is (32 * volume_subdiv)^3")
     ap.add_argument("--streams", type=int, default=1,
                     help="model instances driven side by side on their own HIP streams (2 x --fuse_batches 8 saturates one MI355X; "
@@ -63,6 +68,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.volume_metric and args.host_eval:
         ap.error("--volume_metric is counted on the device only: it cannot be combined with --host_eval")
+    if args.surface_metrics and args.host_eval:
+        ap.error("--surface_metrics is counted on the device only: it cannot be combined with --host_eval")
 
     rank, world = D.init_dist()
     if world == 1:
@@ -79,7 +86,8 @@ def main(argv=None):
     main_stream = torch.cuda.current_stream()
     streams = [torch.cuda.Stream() for _ in range(S)] if S > 1 else [main_stream]
     evaluator = Evaluator(model.mano_models, pa_metrics=args.pa_metrics, curve_metrics=args.curve_metrics,
-                          volume_metric=args.volume_metric, volume_subdiv=args.volume_subdiv, interaction_metrics=args.mrrpe)
+                          volume_metric=args.volume_metric, volume_subdiv=args.volume_subdiv, interaction_metrics=args.mrrpe,
+                          surface_metrics=args.surface_metrics)
     fwd = lambda p, s, t: two_hand.forward_from_packed(model.mano_models["right"], p.cuda(), s.cuda(), t.cuda())[2]
 
     idx, is_pad = D.shard_indices(args.num_samples, args.batchSize, rank, world)
@@ -135,6 +143,8 @@ def main(argv=None):
                         evaluator.update_device_mrrpe(mdl.pred_joints_3d, mdl.buf["gt_joints_3d"], keep=torch.from_numpy(~pad))
                     if args.volume_metric:
                         evaluator.update_device_volume(mdl.pred_right_hand_verts, mdl.pred_left_hand_verts, keep=torch.from_numpy(~pad))
+                    if args.surface_metrics:
+                        evaluator.update_device_surface(mdl.pred_right_hand_verts, mdl.pred_left_hand_verts, keep=torch.from_numpy(~pad))
         for _, st, *_ in jobs:
             main_stream.wait_stream(st)                 # the next round's data generation reuses the instances' MANO handles
     torch.cuda.synchronize()
@@ -150,8 +160,11 @@ def main(argv=None):
     if args.mrrpe:              # of the interaction family the line carries mrrpe: there are no GT meshes to count contact against
         for k in [k for k in m if k.startswith("contact_")]:
             m.pop(k)
+    if args.surface_metrics:    # of the surface family the line carries the three depth metrics: there are no GT meshes here
+        for k in [k for k in m if k.startswith("surface_contact_")]:
+            m.pop(k)
     if rank == 0:
-        for k in ("mpjpe_3d", "inter_mpjpe_3d", "collision_ave", "collision_max") + (("pa_inter_mpjpe_3d", "pa_mpjpe_3d") if args.pa_metrics else ()) + (("pen_volume", "pen_rate") if args.volume_metric else ()) + (("mrrpe",) if args.mrrpe else ()) + curve_keys:
+        for k in ("mpjpe_3d", "inter_mpjpe_3d", "collision_ave", "collision_max") + (("pa_inter_mpjpe_3d", "pa_mpjpe_3d") if args.pa_metrics else ()) + (("pen_volume", "pen_rate") if args.volume_metric else ()) + (("mrrpe",) if args.mrrpe else ()) + (("pen_depth_max", "pen_depth_ave", "pen_vertex_rate") if args.surface_metrics else ()) + curve_keys:
             print(f"{k} : {m[k]:.3f} (optimize)")
         print(json.dumps(dict(num_samples=args.num_samples, world=world, seconds=elapsed, **m)))
     if torch.distributed.is_available() and torch.distributed.is_initialized():

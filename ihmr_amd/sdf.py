@@ -194,6 +194,89 @@ def penetration_volume(verts_right, verts_left, faces_right, faces_left, subdiv=
     return (volume, counts, box, status, bits) if return_bits else (volume, counts, box, status)
 
 
+# ------------------------------------------------------------------------------------------ exact point-to-surface signed distance
+_SURFACE_FACES = {}     # (device, bytes of the table, n_verts, closed) -> (int32 device tensor, F_dist)
+
+
+def _surface_faces(faces, n_verts, close, dev):
+    """``(table, F_dist)``: the face table on ``dev`` -- with ``close`` the fan triangles of :func:`close_boundary` appended, ``F_dist``
+    the original face count -- uploaded once per table and device."""
+    if torch.is_tensor(faces):
+        faces = faces.detach().cpu().numpy()
+    f = np.ascontiguousarray(np.asarray(faces).astype(np.int32))
+    key = (str(dev), f.tobytes(), int(n_verts), bool(close))
+    if key not in _SURFACE_FACES:
+        table = close_boundary(f, n_verts) if close else f
+        if table.ndim != 2 or table.shape[1] != 3 or not 1 <= len(f) <= len(table) <= hip.SURFACE_MAX_FACES:
+            raise ValueError(f"a face table of 1..{hip.SURFACE_MAX_FACES} triangles is needed, got shape {table.shape}")
+        _SURFACE_FACES[key] = (torch.from_numpy(np.ascontiguousarray(table, np.int32)).to(dev), len(f))
+    return _SURFACE_FACES[key]
+
+
+class _SurfaceFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, verts, table, F_dist, signed, use):
+        q, v = points.detach().to(torch.float32).contiguous(), verts.detach().to(points.device, torch.float32).contiguous()
+        B, P, V, dev = q.shape[0], q.shape[1], v.shape[1], q.device
+        dist = torch.empty(B, P, device=dev, dtype=torch.float64)
+        face = torch.empty(B, P, device=dev, dtype=torch.int32)
+        bary = torch.empty(B, P, 3, device=dev, dtype=torch.float64)
+        hip.check(hip.lib().ihmr_surface_distance(q.data_ptr(), P, v.data_ptr(), V, table.data_ptr(), F_dist, len(table),
+                                                  None if use is None else use.data_ptr(), B, int(bool(signed)), dist.data_ptr(),
+                                                  face.data_ptr(), bary.data_ptr(), hip.stream_ptr()), "ihmr_surface_distance")
+        ctx.save_for_backward(q, v, table, dist, face, bary, *(() if use is None else (use,)))
+        ctx.F_dist, ctx.dtypes = F_dist, (points.dtype, verts.dtype)
+        ctx.mark_non_differentiable(face, bary)
+        return dist, face, bary
+
+    @staticmethod
+    def backward(ctx, g_dist, _g_face, _g_bary):
+        q, v, table, dist, face, bary, *rest = ctx.saved_tensors
+        use = rest[0] if rest else None
+        B, P, V = q.shape[0], q.shape[1], v.shape[1]
+        g = g_dist.to(torch.float64).contiguous()
+        d_points = torch.empty_like(q) if ctx.needs_input_grad[0] else None
+        d_verts = torch.empty_like(v) if ctx.needs_input_grad[1] else None
+        hip.check(hip.lib().ihmr_surface_distance_bwd(q.data_ptr(), P, v.data_ptr(), V, table.data_ptr(), ctx.F_dist, len(table),
+                                                      None if use is None else use.data_ptr(), B, dist.data_ptr(), face.data_ptr(),
+                                                      bary.data_ptr(), g.data_ptr(), None if d_points is None else d_points.data_ptr(),
+                                                      None if d_verts is None else d_verts.data_ptr(), hip.stream_ptr()),
+                  "ihmr_surface_distance_bwd")
+        return (None if d_points is None else d_points.to(ctx.dtypes[0]), None if d_verts is None else d_verts.to(ctx.dtypes[1]),
+                None, None, None, None)
+
+
+def surface_distance(points, verts, faces, signed=True, close=True, use=None):
+    """The exact distance from every query point to a triangle mesh (``ihmr_surface_distance``; the definition is DESIGN.md section 8,
+    row (f)8 and ``csrc/surface_pure.h``): ``points`` (B,P,3) and ``verts`` (B,V,3) float32 device tensors, ``faces`` (F,3) an integer
+    table shared by the batch.  ``close=True`` appends the fan triangles of :func:`close_boundary` (MANO's wrist: 1538 + 14): the
+    distance is taken to the original faces only -- the cap is not skin -- and the sign over all of them; tables are cached per device.
+    ``signed=False`` skips the ray work.  ``use`` (B) bool: a sample left out costs nothing and returns zeros (``face`` -1).
+
+    Returns ``(dist, face, bary)``: ``dist`` (B,P) float64 in the inputs' units, negative inside; ``face`` (B,P) int32 the closest face,
+    ``bary`` (B,P,3) float64 the weights of the closest point on its vertices.  A query with a non-finite coordinate has ``dist`` NaN,
+    ``face`` -1.  ``dist`` is differentiable with respect to ``points`` and ``verts`` (``ihmr_surface_distance_bwd``: the same bits on
+    every run), so an attraction or contact term reaches vertices the grid loss of :class:`SDFLoss` cannot: its gradient stops at the
+    other hand's box.  Everything stays on the device; nothing synchronises.
+
+    The exact penetration depth as a heat map (``Evaluator.visualize_result`` paints the grid proxy)::
+
+        d_right, _, _ = surface_distance(right, left, left_faces)               # the right hand's vertices against the left hand
+        d_left, _, _ = surface_distance(left, right, right_faces)
+        depth = torch.clamp(-torch.cat([d_right, d_left], dim=1), min=0)        # (B,1556) metres under the other hand's skin
+        colours = render.penetration_colors(depth, layout="vertex")             # entry k belongs to vertex k of the merged mesh
+    """
+    hip.require_gpu()
+    if points.dim() != 3 or verts.dim() != 3 or points.shape[2] != 3 or verts.shape[2] != 3 or points.shape[0] != verts.shape[0] or points.shape[0] < 1:
+        raise ValueError(f"(B,P,3) points and (B,V,3) vertices of one batch size are needed, got {tuple(points.shape)} and {tuple(verts.shape)}")
+    if points.shape[1] < 1 or not 1 <= verts.shape[1] <= hip.SURFACE_MAX_VERTS:
+        raise ValueError(f"at least one query and 1..{hip.SURFACE_MAX_VERTS} vertices are needed, got {points.shape[1]} and {verts.shape[1]}")
+    dev = points.device
+    table, F_dist = _surface_faces(faces, verts.shape[1], close, dev)
+    u = None if use is None else use.to(dev, torch.uint8).contiguous()
+    return _SurfaceFunction.apply(points, verts, table, F_dist, signed, u)
+
+
 class SDFLoss_Single(nn.Module):  # imported but never used by the reference (loss_utils.py:13)
     def __init__(self, *a, **k):
         super().__init__()

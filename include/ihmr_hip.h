@@ -404,6 +404,34 @@ int ihmr_sdf_volume(const float* verts_a, const int32_t* faces_a, int n_verts_a,
                     const float* verts_b, const int32_t* faces_b, int n_verts_b, int n_faces_b,
                     int B, int subdiv, const uint8_t* keep, float* box, int32_t* status, uint32_t* counts, uint32_t* bits, void* stream);
 
+/* ------------------------------------------------------------------ exact point-to-surface signed distance
+ * The distance from each query point to a triangle mesh, with the sign of inside / outside, the closest face and the weights of the
+ * closest point (csrc/surface_pure.h states the arithmetic down to the operation).  Per sample points
+ * (B,P,3) and verts (B,V,3), float32; one int32 face table (F_total,3) shared by the batch, split as [surface faces 0..F_dist) | cap faces
+ * F_dist..F_total): the distance is taken to the surface faces only, the sign (parity of the +x ray) over all faces, so the table should
+ * describe a closed mesh (ihmr_amd.sdf.close_boundary appends its fan triangles at the end: MANO is [1538 | 14]).  Float64 arithmetic on the
+ * float32 inputs; distances in the inputs' units.
+ *   dist (B,P) float64     +sqrt of the smallest squared distance outside, -sqrt inside; the unsigned value when is_signed == 0 (no ray
+ *                          work).  NaN for a query with a non-finite coordinate or when no surface face is usable.
+ *   face (B,P) int32       the closest surface face (the lowest id on an exact tie), -1 where dist is NaN.
+ *   bary (B,P,3) float64   the weights of the closest point on the face's three vertices, 0 where dist is NaN.
+ *   use (B) or NULL        a sample with use[b] == 0 does no work and has zeros in dist and bary, -1 in face.
+ * A face is left out of distance and sign when it names a vertex outside [0, V), has a non-finite vertex or a normal of squared length 0.
+ *   ihmr_surface_distance_bwd   the gradient of sum(g_dist * dist) from the forward call's inputs and outputs: with c the closest point
+ *                          and n = sign (q - c) / |q - c|, d_points (B,P,3) = g n and d_verts (B,V,3) = the sum over the queries of
+ *                          -w_k g n on the three vertices of each query's face; 0 where |q - c| == 0, dist is 0 or NaN, or face is not a
+ *                          usable id.  Either output may be NULL.  Float64 accumulation in ascending query order, one rounding to
+ *                          float32: the same bits on every run.
+ * -1, nothing launched: a NULL required pointer, B < 1, P < 1, V outside 1..IHMR_SURFACE_MAX_VERTS, F_dist outside 1..F_total,
+ * F_total > IHMR_SURFACE_MAX_FACES.  No allocation, no synchronisation, no workspace. */
+#define IHMR_SURFACE_MAX_VERTS 1024
+#define IHMR_SURFACE_MAX_FACES 2048
+int ihmr_surface_distance(const float* points, int P, const float* verts, int V, const int32_t* faces, int F_dist, int F_total,
+                          const uint8_t* use, int B, int is_signed, double* dist, int32_t* face, double* bary, void* stream);
+int ihmr_surface_distance_bwd(const float* points, int P, const float* verts, int V, const int32_t* faces, int F_dist, int F_total,
+                              const uint8_t* use, int B, const double* dist, const int32_t* face, const double* bary,
+                              const double* g_dist, float* d_points, float* d_verts, void* stream);
+
 /* ------------------------------------------------------------------ packed transfers (round 5)
  * MLPModel.set_input (models/mlp_model.py:120-170) and get_pred_result (:702-719) move 17 + 13 small tensors one copy at a time; one
  * launch does a whole table of them.  A segment = a 2-D strided copy of 32-bit words: dst[r * dst_ld + c] = src[r * src_ld + c] for
