@@ -267,6 +267,15 @@ static int device_cu_count(int* cus_out) {
 extern "C" size_t ihmr_sdf_workspace_bytes(int B) { return sdf_ws_bytes(2 * B) + (size_t)2 * NFP * 4 * 4 + 256; }
 
 static int g_collect_stats = 0;
+// checker switch: sdf_prep_kernel neither fills nor reads its LDS copy of the packed face table -- every (triangle, column) pair of the
+// ray-parity phase gathers its face word from global memory.  The same bits and the same work either way (tests/test_gpu_prep_faces.py);
+// never set in the product path.  Read when a launch is issued: a captured graph keeps what it was captured with.
+static int g_prep_global_faces = 0;
+extern "C" int ihmr_debug_prep_global_faces(int force) {
+    const int prev = g_prep_global_faces;
+    g_prep_global_faces = force ? 1 : 0;
+    return prev;
+}
 
 static int sdf_launch(const VertLayout& vl, const int32_t* faces_r_soa, const int32_t* faces_l_soa, const uint32_t* fpk_r,
                       const uint32_t* fpk_l, int B, SdfWorkspace ws, float robustifier, float* loss, float* per_vert, float* origin, float* dval, bool dense, hipStream_t st) {
@@ -281,13 +290,13 @@ static int sdf_launch(const VertLayout& vl, const int32_t* faces_r_soa, const in
     if (timed) { if (int rc = timed_begin(&tcur, st)) return rc; }
     if (prep == plan::PREP_DENSE)
         hipLaunchKernelGGL((sdf_prep_kernel<true, SDF_PREP_THREADS_LARGE>), dim3(2 * B), dim3(SDF_PREP_THREADS_LARGE), 0, st, vl, B, faces_r_soa,
-                           faces_l_soa, ws, g_collect_stats);
+                           faces_l_soa, ws, g_collect_stats, g_prep_global_faces);
     else if (prep == plan::PREP_SMALL)
         hipLaunchKernelGGL((sdf_prep_kernel<false, SDF_PREP_THREADS_SMALL>), dim3(2 * B), dim3(SDF_PREP_THREADS_SMALL), 0, st, vl, B, faces_r_soa,
-                           faces_l_soa, ws, g_collect_stats);
+                           faces_l_soa, ws, g_collect_stats, g_prep_global_faces);
     else
         hipLaunchKernelGGL((sdf_prep_kernel<false, SDF_PREP_THREADS_LARGE>), dim3(2 * B), dim3(SDF_PREP_THREADS_LARGE), 0, st, vl, B, faces_r_soa,
-                           faces_l_soa, ws, g_collect_stats);
+                           faces_l_soa, ws, g_collect_stats, g_prep_global_faces);
     // persistent grid: as many workgroups as the GPU holds at once; they pull work units from a queue (sdf_collision.h)
     int cus = 0;
     if (int rc = device_cu_count(&cus)) return rc;
@@ -1246,17 +1255,19 @@ extern "C" int ihmr_flush_kernel_timer(void) {
 
 
 #ifdef SDF_STAMPS
-// experiment builds only (scripts/sdf_stamps.py): zero = 1 clears the per-wave phase sums, zero = 0 copies them to the host (4096 * 4 * 8 int64)
+// experiment builds only (scripts/sdf_stamps.py): zero = 1 clears the per-wave phase sums, zero = 0 copies them to the host (4096 * (4 * 12 + 8 + 4) int64: g_sdf_stamps, g_sdf_span, g_sdf_prep, g_sdf_prep2)
 extern "C" int ihmr_debug_stamps(long long* host, int zero) {
     HIP_TRY(hipDeviceSynchronize());
     if (zero) {
         void* p; HIP_TRY(hipGetSymbolAddress(&p, HIP_SYMBOL(g_sdf_stamps))); HIP_TRY(hipMemset(p, 0, sizeof(long long) * 4096 * 4 * 8));
         HIP_TRY(hipGetSymbolAddress(&p, HIP_SYMBOL(g_sdf_prep))); HIP_TRY(hipMemset(p, 0, sizeof(long long) * 4096 * 8));
+        HIP_TRY(hipGetSymbolAddress(&p, HIP_SYMBOL(g_sdf_prep2))); HIP_TRY(hipMemset(p, 0, sizeof(long long) * 4096 * 4));
         return 0;
     }
     HIP_TRY(hipMemcpyFromSymbol(host, HIP_SYMBOL(g_sdf_stamps), sizeof(long long) * 4096 * 4 * 8));
     HIP_TRY(hipMemcpyFromSymbol(host + 4096 * 4 * 8, HIP_SYMBOL(g_sdf_span), sizeof(long long) * 4096 * 4 * 4));
     HIP_TRY(hipMemcpyFromSymbol(host + 4096 * 4 * 12, HIP_SYMBOL(g_sdf_prep), sizeof(long long) * 4096 * 8));
+    HIP_TRY(hipMemcpyFromSymbol(host + 4096 * 4 * 12 + 4096 * 8, HIP_SYMBOL(g_sdf_prep2), sizeof(long long) * 4096 * 4));
     return 0;
 }
 #endif

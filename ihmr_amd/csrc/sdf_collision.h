@@ -230,15 +230,16 @@ struct VertLayout {
 // size, the layout stays linear).  Asynchronous: the caller goes on issuing its other loads and closes with SDF_STAGE_CLOSE():
 // every wave waits for its OWN outstanding vector-memory operations (s_waitcnt vmcnt(0): the DMA writes to LDS are tracked by the
 // issuing wave's vmcnt only -- a workgroup barrier alone does not wait for them), then the barrier makes all waves' pieces visible
-// to all (the form of CK's block_sync_lds_direct_load).  n16 16-byte units by 256 threads.
+// to all (the form of CK's block_sync_lds_direct_load).  n16 16-byte units by THREADS threads (256 unless the caller says otherwise).
 #define SDF_STAGE_CLOSE() do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); } while (0)
 // ... the same, but the wave's YOUNGEST vector-memory load may stay in flight (loads return in order: when at most one operation is
 // outstanding, every load older than the youngest -- the DMA pieces, issued first -- has returned; outstanding stores of an earlier
 // phase only make the wait longer).  The caller issues exactly such a load last (a prefetch nobody waits for here).
 #define SDF_STAGE_CLOSE_KEEP1() do { asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); __syncthreads(); } while (0)
+template <int THREADS = SDF_THREADS>
 __device__ __forceinline__ void sdf_stage_async(const void* __restrict__ src, char* dst_lds, int n16) {
     const int tid = threadIdx.x, wave = tid / WAVE;
-    for (int base = wave * WAVE; base < n16; base += SDF_THREADS) {
+    for (int base = wave * WAVE; base < n16; base += THREADS) {
         if (base + (tid % WAVE) < n16)
             __builtin_amdgcn_global_load_lds(reinterpret_cast<const char*>(src) + (size_t)(base + tid % WAVE) * 16,
                                              (__attribute__((address_space(3))) void*)(dst_lds + (size_t)base * 16), 16, 0, 0);
@@ -282,6 +283,8 @@ __device__ __forceinline__ int block_excl_scan_1024(int* data, int* scratch /* >
 __device__ long long g_sdf_stamps[4096 * 4][8];       // per (workgroup, wave) sums, plain stores: no atomics in a stamped launch
 __device__ long long g_sdf_span[4096 * 4][4];         // entry / exit stamp, XCC id, items of the LAST launch (either search)
 __device__ long long g_sdf_prep[4096][8];             // sdf_prep_kernel: phase sums per hand (wave 0), [7] = launches
+__device__ long long g_sdf_prep2[4096][4];            // ... its ray-parity phase split: [0] enumerate + scan + queue, [1] the pair loop up to the
+                                                      // phase's closing barrier (cycles), [2] pairs P, [3] trips of the pair loop (P / PT, rounded up)
 #else
 #define SDF_TK(...)
 #define SDF_STAMP() 0ll
@@ -310,7 +313,7 @@ __device__ unsigned g_handlog_n = 0, g_handlog_cap = 0;
 template <bool DENSE, int PT>
 __global__ __launch_bounds__(PT, SDF_PREP_MIN_WAVES) void sdf_prep_kernel(VertLayout vl, int B, const int32_t* __restrict__ faces_r,
                                                                     const int32_t* __restrict__ faces_l, SdfWorkspace ws,
-                                                                    int collect_stats) {
+                                                                    int collect_stats, int global_faces) {
     TL_SCOPE(1);
     constexpr int CPT = SDF_NCOL / PT;             // adjacent grid columns owned by a thread
     constexpr int VPT = (NV + PT - 1) / PT;         // vertices owned by a thread
@@ -318,7 +321,13 @@ __global__ __launch_bounds__(PT, SDF_PREP_MIN_WAVES) void sdf_prep_kernel(VertLa
     __shared__ unsigned needed[SDF_NCOL];
     __shared__ unsigned rowany[SDF_G];      // bit j of word k: column (k,j) has a needed voxel
     __shared__ unsigned parity[SDF_NCOL];
-    __shared__ int cur[SDF_NCOL];
+    // one array, two tenants.  ftab: the packed face table of the hand's side (NFP words), DMA'd at the top of the kernel and read by
+    // the pair loop of the ray-parity phase -- a hand that is not static leaves `cur` alone until the publish phase, which overwrites
+    // the table's first SDF_NCOL words (nothing behind the ray-parity phase reads the table).  A static hand uses `cur` in between
+    // (`newm`) and reads the few faces it needs from global memory.
+    __shared__ __attribute__((aligned(16))) unsigned ftab[NFP];
+    int* const cur = reinterpret_cast<int*>(ftab);
+    static_assert(NFP >= SDF_NCOL && NFP % 4 == 0 && NFP <= 2048, "cur lives in the face table's first words; the table is staged in 16-byte units");
     __shared__ float red[6][PT / WAVE];
     __shared__ float red_disp[PT / WAVE];   // per wave: how far its vertices have moved from the reference pose of the hand's candidate lists
     __shared__ int scratch[PT / WAVE];
@@ -341,6 +350,10 @@ __global__ __launch_bounds__(PT, SDF_PREP_MIN_WAVES) void sdf_prep_kernel(VertLa
     const bool stat = lists_on && !ws.force_rebuild && ((ws.static_mask >> hnd) & 1);
     // ... and one that only translates (SdfWorkspace::moving_box): static in its own frame, the box follows the current vertices
     const bool tbox = stat && ((ws.moving_box >> hnd) & 1);
+    // the face table of the hand's side -> LDS, no register held (global_faces: the checker switch ihmr_debug_prep_global_faces, nobody
+    // fills or reads the LDS table); uniform over the workgroup.  Closed at the barrier in front of the pair loop, see there
+    const bool faces_lds = !stat && !global_faces;
+    if (faces_lds) sdf_stage_async<PT>(ws.fpk[hnd], reinterpret_cast<char*>(ftab), NFP / 4);
 #pragma unroll
     for (int rep = 0; rep < VPT; ++rep) {
         oq[rep][0] = oq[rep][1] = oq[rep][2] = 0.f;
@@ -544,8 +557,8 @@ __global__ __launch_bounds__(PT, SDF_PREP_MIN_WAVES) void sdf_prep_kernel(VertLa
     SDF_TK(pk_[3] = SDF_STAMP();)
     float4* sph = ws.sph + (size_t)H * NFP;
     unsigned* nrm = ws.nrm + (size_t)H * NFP;
-    unsigned long long st_tests = 0;
-    SDF_TK(pk_[4] = SDF_STAMP();)
+    unsigned st_tests = 0;      // (a thread's share: <= 1538 x 1024 pairs / PT, 33 tests each -- 32 bits hold it, and the pair loop has no register to spare)
+    SDF_TK(pk_[4] = SDF_STAMP(); long long pq_ = 0; int pairs_ = 0;)
     // ---- ray parity as DENSE (triangle, needed column) pairs.  A triangle-parallel loop over the needed columns of each triangle's
     //      yz box is bound by its slowest lane (stamps: 5 us on average, 16 us for the slowest hand of a launch -- a palm triangle
     //      covers 30 columns, most cover 0-2, and every iteration is a dependent LDS round trip).  So the lanes only ENUMERATE their
@@ -605,12 +618,17 @@ __global__ __launch_bounds__(PT, SDF_PREP_MIN_WAVES) void sdf_prep_kernel(VertLa
                     }
                 }
             }
+            // (the face table: this wave's pieces have landed -- the DMA writes are tracked by the issuing wave's vmcnt only -- and the
+            // barrier publishes them.  Waiting here costs nothing, with or without a table: what is outstanding was issued phases ago;
+            // at the kernel's first barrier the same wait held every wave for its youngest load, +0.3 us per hand in the stamps)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             SDF_LDS_BARRIER();
+            SDF_TK(if (win == 0) { pq_ = SDF_STAMP(); pairs_ = P; })
             const int nwin = min(P - win, SDF_RAYQ);
             for (int q = tid; q < nwin; q += PT) {
                 const unsigned e = rayq[q];
                 const int col = (int)(e >> 11);
-                const unsigned pk = fpk[e & 2047u];
+                const unsigned pk = faces_lds ? ftab[e & 2047u] : fpk[e & 2047u];      // (the same word; with the table in LDS no trip leaves the CU)
                 const int fa = (int)(pk & 1023u), fb = (int)((pk >> 10) & 1023u), fc = (int)(pk >> 20);
                 const float a[3] = {vn[3 * fa], vn[3 * fa + 1], vn[3 * fa + 2]};
                 const float bb[3] = {vn[3 * fb], vn[3 * fb + 1], vn[3 * fb + 2]};
@@ -636,6 +654,7 @@ __global__ __launch_bounds__(PT, SDF_PREP_MIN_WAVES) void sdf_prep_kernel(VertLa
             rb2[rep] = ws.rbits[(size_t)H * SDF_NCOL + CPT * tid + rep];
         }
     }
+    SDF_TK(if (!pq_) pq_ = SDF_STAMP();)            // (no pair: the whole phase counts as enumerate + scan)
     SDF_LDS_BARRIER();
     SDF_TK(pk_[5] = SDF_STAMP();)
     // ---- publish: a thread owns CPT adjacent columns; phi = 0 for the outside voxels a sample reads, inside voxels
@@ -805,7 +824,8 @@ __global__ __launch_bounds__(PT, SDF_PREP_MIN_WAVES) void sdf_prep_kernel(VertLa
             nrm[f] = real ? nw : SDF_NRM_NOPLANE;
         }
     }
-    SDF_TK(if (tid == 0 && H < 4096) { pk_[6] = SDF_STAMP(); for (int k = 0; k < 6; ++k) g_sdf_prep[H][k] += pk_[k + 1] - pk_[k]; g_sdf_prep[H][6] += (long long)blk_inside; g_sdf_prep[H][7] += 1; })
+    SDF_TK(if (tid == 0 && H < 4096) { pk_[6] = SDF_STAMP(); for (int k = 0; k < 6; ++k) g_sdf_prep[H][k] += pk_[k + 1] - pk_[k]; g_sdf_prep[H][6] += (long long)blk_inside; g_sdf_prep[H][7] += 1;
+                                      g_sdf_prep2[H][0] += pq_ - pk_[4]; g_sdf_prep2[H][1] += pk_[5] - pq_; g_sdf_prep2[H][2] += pairs_; g_sdf_prep2[H][3] += (pairs_ + PT - 1) / PT; })
     if (collect_stats) {
         unsigned long long c = st_tests;
 #pragma unroll

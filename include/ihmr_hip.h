@@ -722,6 +722,11 @@ int ihmr_debug_force_full_skin(int force);
  * hand whose axis-angles the stage does not refine keeps the rotations of its skeleton record).  The two produce the same bits
  * (tests/test_gpu_stage_tails.py).  Returns the previous value. */
 int ihmr_debug_force_generic_tail(int force);
+/* checker switch (tests and A/B runs only): force = 1 makes the collision prep kernel gather the packed face word of every (triangle,
+ * column) pair of its ray-parity phase from global memory; 0 restores the default (a hand that is not static stages its side's face
+ * table in LDS at the top of the kernel and the pairs read it there).  The two produce the same bits and do the same work
+ * (tests/test_gpu_prep_faces.py).  Read when a launch is issued: a captured graph keeps its value.  Returns the previous value. */
+int ihmr_debug_prep_global_faces(int force);
 
 const char* ihmr_version(void);
 

@@ -17,8 +17,8 @@ L = hip.lib(); L.ihmr_debug_stamps.argtypes = [C.c_void_p, C.c_int]
 m.set_input(inp); m.init_optimize(); m.run_stage(m.strategy[0])
 L.ihmr_debug_stamps(None, 1)
 m.run_stage(m.strategy[1]); torch.cuda.synchronize()
-raw = np.zeros(4096 * 4 * 12 + 4096 * 8, np.int64); L.ihmr_debug_stamps(raw.ctypes.data, 0)
-prep = raw[4096 * 4 * 12:].reshape(-1, 8); prep = prep[prep[:, 7] > 0]
+raw = np.zeros(4096 * (4 * 12 + 8 + 4), np.int64); L.ihmr_debug_stamps(raw.ctypes.data, 0)
+prep = raw[4096 * 4 * 12:4096 * (4 * 12 + 8)].reshape(-1, 8); prep = prep[prep[:, 7] > 0]
 ray = prep[:, 4] / prep[:, 7] / 2400.0; P = prep[:, 6] / prep[:, 7]
 print("hands", len(prep), "P mean", P.mean(), "p90", np.percentile(P, 90), "max", P.max(), "frac > 4096", (P > 4096).mean())
 order = np.argsort(ray)

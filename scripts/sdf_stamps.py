@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Phase times of sdf_dist_kernel's work items from an experiment build (-DSDF_STAMPS=1 list search / =2 full search):
-   hipcc ... -DSDF_STAMPS=1 ihmr_hip.hip -o build/stamps1.so ;  IHMR_HIP_LIBRARY=build/stamps1.so python3 scripts/sdf_stamps.py [fuse]
+   hipcc ... -DSDF_STAMPS=1 -DSDF_PREP_MIN_WAVES=4 ihmr_hip.hip -o build/stamps1.so ;  IHMR_HIP_LIBRARY=build/stamps1.so python3 scripts/sdf_stamps.py [fuse] [global]
 Runs one stage of the refinement at `fuse` x 64 samples per launch with the counters on and prints the mean shader-clock cycles per
-item and phase (summed per wave by the kernel into the spare counter slots)."""
+item and phase (summed per wave by the kernel into the spare counter slots), and the prep kernel's phases per hand with its ray-parity
+phase split into enumerate + scan and the pair loop, the latter fitted against the hand's pair-loop trips.  `global`: with the checker
+switch ihmr_debug_prep_global_faces set (the pairs gather their face words from global memory, as before the LDS face table).
+-DSDF_PREP_MIN_WAVES=4: the stamps live in scalar registers, and at the product's budget of 64 vector registers the stamped 512-thread prep
+kernel spills to scratch -- a spilling form of that kernel is not run; check the built code object first."""
 import ctypes as C, os, sys, types
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -16,6 +20,9 @@ B = 64
 o = types.SimpleNamespace(isTrain=False, dist=False, process_rank=-1, batchSize=B, inputSize=224, num_joints=42, total_params_dim=122,
                           cam_params_dim=3, pose_params_dim=96, shape_params_dim=20, trans_params_dim=3, model_root="", strategy="opt_default",
                           save_mid_freq=10, optimizer="adam", opt_epoch=49, fuse_batches=G)
+if len(sys.argv) > 2 and sys.argv[2] == "global":
+    hip.lib().ihmr_debug_prep_global_faces(1)          # before anything is captured: a graph keeps the value it was captured with
+    print("ihmr_debug_prep_global_faces(1): face words from global memory")
 m = OptimizeModel(o)
 fwd = lambda p, s, t: two_hand.forward_from_packed(m.mano_models["right"], p.cuda(), s.cuda(), t.cuda())[2]
 bs = [synthetic_opt_batch(B, fwd, seed=1234 + 1000 * i) for i in range(G)]
@@ -36,15 +43,28 @@ for stage_id in (1, 3):
     t0 = time.perf_counter()
     m.run_stage(m.strategy[stage_id]); torch.cuda.synchronize()
     wall = time.perf_counter() - t0
-    raw = np.zeros(4096 * 4 * 12 + 4096 * 8, np.int64)
+    raw = np.zeros(4096 * (4 * 12 + 8 + 4), np.int64)
     L.ihmr_debug_stamps(raw.ctypes.data, 0)
     buf, span = raw[:4096 * 4 * 8].reshape(-1, 8), raw[4096 * 4 * 8:4096 * 4 * 12].reshape(-1, 4)
-    prep = raw[4096 * 4 * 12:].reshape(-1, 8)
+    prep = raw[4096 * 4 * 12:4096 * (4 * 12 + 8)].reshape(-1, 8)
+    prep2 = raw[4096 * (4 * 12 + 8):].reshape(-1, 4)[prep[:, 7] > 0]
     prep = prep[prep[:, 7] > 0]
     if len(prep):
         ph = prep[:, :6] / prep[:, 7:8] / 2400.0
         tot = ph.sum(1)
         print('   prep per hand [us]: ' + '; '.join(f'{n} {ph[:, k].mean():.2f} (max {ph[:, k].max():.2f})' for k, n in enumerate(['loads+box', 'normalise+needed', 'list state', 'records', 'ray parity', 'publish'])) + f'; total mean {tot.mean():.2f} p90 {np.percentile(tot, 90):.2f} max {tot.max():.2f}')
+        # the ray-parity phase, split: (a) enumerate + scan + queue, (b) the pair loop up to the closing barrier; per hand, means over the launches
+        n = prep[:, 7].astype(float)
+        ea, lb, P, trips = prep2[:, 0] / n / 2400.0, prep2[:, 1] / n / 2400.0, prep2[:, 2] / n, prep2[:, 3] / n
+        stat = lambda x: f'mean {x.mean():.2f} p90 {np.percentile(x, 90):.2f} max {x.max():.2f}'
+        print(f'   ray parity per hand [us]: whole {stat(ph[:, 4])}; (a) enumerate+scan {stat(ea)}; (b) pair loop {stat(lb)}; '
+              f'pairs P mean {P.mean():.0f} p90 {np.percentile(P, 90):.0f} max {P.max():.0f}; trips mean {trips.mean():.2f} max {trips.max():.2f}')
+        w = P > 0
+        if w.sum() > 2 and np.ptp(trips[w]) > 0:
+            c = np.polyfit(trips[w], lb[w], 1)
+            print(f'   (b) against trips, hands with pairs ({int(w.sum())}): {c[0]:.3f} us per trip + {c[1]:.2f} us; against P: '
+                  f'{1000 * np.polyfit(P[w], lb[w], 1)[0]:.2f} us per 1000 pairs; hand with most pairs: P {P.max():.0f}, (a) {ea[P.argmax()]:.2f}, (b) {lb[P.argmax()]:.2f}, '
+                  f'whole kernel {tot[P.argmax()]:.2f} us')
     sp = span[span[:, 1] > 0]
     # the shader clocks of the XCDs are not aligned with each other: times relative to the first wave start of the same XCD
     xcd = (sp[:, 2] % 8).astype(int)
