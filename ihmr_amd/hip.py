@@ -32,26 +32,6 @@ PARAM_BLOCKS = dict(pred_cam_params=(1, 0, 3), pred_hand_trans=(2, 3, 3), pred_r
 LOSS_IDS = dict(joints_2d_loss_p=0, joints_3d_loss_p=1, collision_loss=2)
 OPTIMIZERS = dict(adam=0, sgd=1)
 
-# every symbol include/ihmr_hip.h declares (checked by the CPU test-suite against the built library)
-EXPORTED_SYMBOLS = [
-    "ihmr_mano_create", "ihmr_mano_destroy", "ihmr_mano_update_shapedirs", "ihmr_mano_workspace_bytes", "ihmr_mano_lbs_fwd",
-    "ihmr_mano_lbs_bwd",
-    "ihmr_sdf_workspace_bytes", "ihmr_sdf_collision", "ihmr_sdf_collision_ex", "ihmr_sdf_dense_grid", "ihmr_opt_workspace_bytes",
-    "ihmr_opt_run_stage", "ihmr_opt_forward_losses", "ihmr_opt_sdf_stats", "ihmr_opt_sdf_counters", "ihmr_opt_sdf_inside_bits", "ihmr_opt_stage_graph_create",
-    "ihmr_opt_forward_graph_create", "ihmr_graph_launch", "ihmr_graph_destroy", "ihmr_opt_set_params", "ihmr_eval_metrics", "ihmr_eval_mpvpe", "ihmr_eval_pa_joints", "ihmr_eval_pa_verts",
-    "ihmr_eval_curve_joints", "ihmr_eval_curve_verts", "ihmr_eval_mrrpe", "ihmr_eval_contact", "ihmr_sdf_volume", "ihmr_surface_distance", "ihmr_surface_distance_bwd", "ihmr_conv_igemm", "ihmr_maxpool3x3s2",
-    "ihmr_avgpool_relu", "ihmr_preprocess_images", "ihmr_mlp_train_grad", "ihmr_transpose", "ihmr_relu_backward", "ihmr_colsum",
-    "ihmr_adam_step", "ihmr_bn_workspace_bytes", "ihmr_bn_train_forward", "ihmr_bn_train_backward", "ihmr_conv_wgrad",
-    "ihmr_dilate2", "ihmr_interleave2", "ihmr_pack_dgrad_weight", "ihmr_maxpool3x3s2_backward", "ihmr_avgpool_relu_backward", "ihmr_set_kernel_timer", "ihmr_flush_kernel_timer",
-    "ihmr_mlp_workspace_bytes", "ihmr_mlp_stage_head", "ihmr_mlp_forward_select", "ihmr_mlp_camera_select", "ihmr_opt_forward_verts",
-    "ihmr_debug_force_lbs_bwd2_streaming", "ihmr_debug_force_full_skin", "ihmr_debug_force_generic_tail", "ihmr_debug_prep_global_faces", "ihmr_version", "ihmr_copy_segments", "ihmr_root_align_joints",
-    "ihmr_augment_images", "ihmr_augment_labels",
-    "ihmr_render_workspace_bytes", "ihmr_render_meshes", "ihmr_draw_keypoints",
-    "ihmr_view_vertices", "ihmr_heat_colours", "ihmr_paint_meshes",
-    "ihmr_conv_igemm_bf16", "ihmr_pack_image_bf16", "ihmr_maxpool3x3s2_bf16", "ihmr_avgpool_relu_bf16", "ihmr_cast_f32_bf16",
-]
-
-
 class ManoArrays(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("v_template", "shapedirs", "posedirs", "J_regressor", "lbs_weights", "parents",
                                           "hands_mean", "faces", "tip_ids")]
@@ -158,6 +138,105 @@ class KernelTimer(C.Structure):
         return self.ms[k] / self.n[k] - (self.ms_event_pair / self.n_event_pair if self.n_event_pair > 0 else 0.0)
 
 
+_vp, _i, _f, _z, _P = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.POINTER
+_conv = [_vp] * 5 + [_i] * 16 + [_vp, _z, _vp]
+_raster = [_vp] * 4 + [_i] * 3 + [_vp] * 3 + [_P(RenderLights), _vp, _i, _vp, _vp, _vp, _i, _vp]
+# THE binding: name -> (restype, argtypes) of every function include/ihmr_hip.h declares, in the header's own terms (a handle, a
+# stream and a device pointer are c_void_p; a struct travels as a pointer to its ctypes mirror above).  lib() applies it;
+# tests/test_abi_cpu.py compares it with the header's prototypes argument by argument and the mirrors with the compiler's layout.
+SIGNATURES = {
+    "ihmr_mano_create": (_i, [_P(ManoArrays), _P(_vp)]),
+    "ihmr_mano_destroy": (_i, [_vp]),
+    "ihmr_mano_update_shapedirs": (_i, [_vp, _vp]),
+    "ihmr_mano_workspace_bytes": (_z, [_i]),
+    "ihmr_mano_lbs_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "ihmr_mano_lbs_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "ihmr_sdf_workspace_bytes": (_z, [_i]),
+    "ihmr_sdf_collision": (_i, [_vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ihmr_sdf_collision_ex": (_i, [_vp, _vp, _vp, _i, _f, _P(SdfOptions), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ihmr_sdf_dense_grid": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "ihmr_opt_workspace_bytes": (_z, [_i]),
+    "ihmr_opt_run_stage": (_i, [_vp, _vp, _P(OptIO), _i, _P(OptWeights), _P(OptStage), _vp]),
+    "ihmr_opt_forward_losses": (_i, [_vp, _vp, _P(OptIO), _i, _P(OptWeights), _vp]),
+    "ihmr_opt_sdf_stats": (_i, [_vp, _vp, _P(OptIO), _i, _P(OptWeights), _vp, _vp]),
+    "ihmr_opt_sdf_counters": (_i, [_P(OptIO), _i, _vp, _i]),
+    "ihmr_opt_sdf_inside_bits": (_i, [_P(OptIO), _i, _vp, _vp]),
+    "ihmr_opt_stage_graph_create": (_i, [_vp, _vp, _P(OptIO), _i, _P(OptWeights), _P(OptStage), _P(_vp)]),
+    "ihmr_opt_forward_graph_create": (_i, [_vp, _vp, _P(OptIO), _i, _P(OptWeights), _P(_vp)]),
+    "ihmr_graph_launch": (_i, [_vp, _vp]),
+    "ihmr_graph_destroy": (_i, [_vp]),
+    "ihmr_opt_set_params": (_i, [_P(OptIO), _vp, _i, _vp]),
+    "ihmr_eval_metrics": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "ihmr_eval_mpvpe": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "ihmr_eval_pa_joints": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "ihmr_eval_pa_verts": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "ihmr_eval_curve_joints": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "ihmr_eval_curve_verts": (_i, [_vp] * 7 + [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "ihmr_eval_mrrpe": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "ihmr_eval_contact": (_i, [_vp] * 7 + [_i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "ihmr_sdf_volume": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ihmr_surface_distance": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "ihmr_surface_distance_bwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ihmr_conv_igemm": (_i, _conv),
+    "ihmr_maxpool3x3s2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "ihmr_avgpool_relu": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "ihmr_preprocess_images": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ihmr_mlp_train_grad": (_i, [_vp, _vp, _P(OptIO), _i, _P(OptWeights), _P(TrainWeights)] + [_vp] * 8 + [_i, _vp, _i, _vp]),
+    "ihmr_transpose": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "ihmr_relu_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "ihmr_colsum": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "ihmr_adam_step": (_i, [_vp, _vp, _vp, _vp, _z, _f, _f, _f, _f, _f, _i, _vp]),
+    "ihmr_bn_workspace_bytes": (_z, [_i]),
+    "ihmr_bn_train_forward": (_i, [_vp, C.c_long, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
+    "ihmr_bn_train_backward": (_i, [_vp, _vp, C.c_long, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ihmr_conv_wgrad": (_i, [_vp, _vp, _vp] + [_i] * 14 + [_vp, _z, _vp]),
+    "ihmr_dilate2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "ihmr_interleave2": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ihmr_pack_dgrad_weight": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "ihmr_maxpool3x3s2_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "ihmr_avgpool_relu_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ihmr_set_kernel_timer": (_i, [_P(KernelTimer)]),
+    "ihmr_flush_kernel_timer": (_i, []),
+    "ihmr_mlp_workspace_bytes": (_z, [_i]),
+    "ihmr_mlp_stage_head": (_i, [_P(MlpNet), _P(MlpTables), _P(OptIO), _i, _vp, _vp]),
+    "ihmr_mlp_forward_select": (_i, [_vp, _vp, _P(OptIO), _i, _P(OptWeights), _P(MlpTables), _P(MlpStage), _i, _vp, _vp]),
+    "ihmr_mlp_camera_select": (_i, [_P(OptIO), _i, _P(OptWeights), _P(MlpTables), _P(MlpStage), _vp, _vp]),
+    "ihmr_opt_forward_verts": (_i, [_vp, _P(OptIO), _i, _vp]),
+    "ihmr_debug_force_lbs_bwd2_streaming": (_i, [_i]),
+    "ihmr_debug_force_full_skin": (_i, [_i]),
+    "ihmr_debug_force_generic_tail": (_i, [_i]),
+    "ihmr_debug_prep_global_faces": (_i, [_i]),
+    "ihmr_version": (C.c_char_p, []),
+    "ihmr_copy_segments": (_i, [_P(CopySeg), _i, _vp]),
+    "ihmr_root_align_joints": (_i, [_vp, _vp, _i, _vp]),
+    "ihmr_augment_images": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _P(_i), _vp]),
+    "ihmr_augment_labels": (_i, [_vp, _vp, _i, _i] + [_vp] * 15),
+    "ihmr_render_workspace_bytes": (_z, [_i, _i]),
+    "ihmr_render_meshes": (_i, _raster),
+    "ihmr_draw_keypoints": (_i, [_vp, _vp, _vp, C.c_char_p, _i, _i, _i, _vp]),
+    "ihmr_view_vertices": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp]),
+    "ihmr_heat_colours": (_i, [_vp, _vp, _P(_f * 3), _f, _f, _i, _i, _i, _vp, _i, _vp]),
+    "ihmr_paint_meshes": (_i, _raster),
+    "ihmr_conv_igemm_bf16": (_i, _conv),
+    "ihmr_pack_image_bf16": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "ihmr_maxpool3x3s2_bf16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "ihmr_avgpool_relu_bf16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "ihmr_cast_f32_bf16": (_i, [_vp, _vp, _z, _vp]),
+}
+EXPORTED_SYMBOLS = list(SIGNATURES)      # every symbol include/ihmr_hip.h declares
+
+
+def bind(L):
+    """Give every function of SIGNATURES that the loaded library `L` exports its restype and argtypes.  One rule for a library
+    that lacks a symbol (an older build named with IHMR_HIP_LIBRARY for an A/B run against the parent commit): it is skipped, and
+    a call of it raises AttributeError.  The product library is checked for every symbol where it is built."""
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+    return L
+
+
 def sources():
     return sorted(osp.join(SRC_DIR, f) for f in os.listdir(SRC_DIR) if f.endswith((".hip", ".h"))) + [
         osp.join(osp.dirname(_HERE), "include", "ihmr_hip.h")]
@@ -252,97 +331,11 @@ def _resolve_library() -> str:
 
 
 def lib():
-    """Load (building on demand when hipcc is present).  Raises if unavailable -- never falls back."""
+    """Load (building on demand when hipcc is present) and bind (see bind() for a library that lacks a symbol).  Raises if
+    unavailable -- never falls back."""
     global _LIB
     if _LIB is None:
-        L = C.CDLL(_resolve_library())
-        vp, i, f = C.c_void_p, C.c_int, C.c_float
-        L.ihmr_mano_create.argtypes = [C.POINTER(ManoArrays), C.POINTER(vp)]
-        L.ihmr_mano_destroy.argtypes = [vp]
-        L.ihmr_mano_update_shapedirs.argtypes = [vp, vp]
-        L.ihmr_mano_workspace_bytes.argtypes = [i]
-        L.ihmr_mano_workspace_bytes.restype = C.c_size_t
-        L.ihmr_mano_lbs_fwd.argtypes = [vp, vp, vp, vp, i, vp, vp, vp, vp]
-        L.ihmr_mano_lbs_bwd.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, i, vp]
-        L.ihmr_sdf_workspace_bytes.argtypes = [i]
-        L.ihmr_sdf_workspace_bytes.restype = C.c_size_t
-        L.ihmr_sdf_collision.argtypes = [vp, vp, vp, i, f, vp, vp, vp, vp, vp, vp]
-        L.ihmr_sdf_collision_ex.argtypes = [vp, vp, vp, i, f, C.POINTER(SdfOptions), vp, vp, vp, vp, vp, vp]
-        L.ihmr_sdf_dense_grid.argtypes = [vp, vp, vp, i, vp, vp, vp]
-        L.ihmr_opt_workspace_bytes.argtypes = [i]
-        L.ihmr_opt_workspace_bytes.restype = C.c_size_t
-        L.ihmr_opt_run_stage.argtypes = [vp, vp, C.POINTER(OptIO), i, C.POINTER(OptWeights), C.POINTER(OptStage), vp]
-        L.ihmr_opt_forward_losses.argtypes = [vp, vp, C.POINTER(OptIO), i, C.POINTER(OptWeights), vp]
-        L.ihmr_opt_stage_graph_create.argtypes = [vp, vp, C.POINTER(OptIO), i, C.POINTER(OptWeights), C.POINTER(OptStage), C.POINTER(vp)]
-        L.ihmr_opt_forward_graph_create.argtypes = [vp, vp, C.POINTER(OptIO), i, C.POINTER(OptWeights), C.POINTER(vp)]
-        L.ihmr_graph_launch.argtypes = [vp, vp]
-        L.ihmr_opt_set_params.argtypes = [C.POINTER(OptIO), vp, i, vp]
-        L.ihmr_mlp_workspace_bytes.argtypes = [i]
-        L.ihmr_mlp_workspace_bytes.restype = C.c_size_t
-        L.ihmr_mlp_stage_head.argtypes = [C.POINTER(MlpNet), C.POINTER(MlpTables), C.POINTER(OptIO), i, vp, vp]
-        L.ihmr_mlp_forward_select.argtypes = [vp, vp, C.POINTER(OptIO), i, C.POINTER(OptWeights), C.POINTER(MlpTables), C.POINTER(MlpStage), i, vp, vp]
-        L.ihmr_mlp_camera_select.argtypes = [C.POINTER(OptIO), i, C.POINTER(OptWeights), C.POINTER(MlpTables), C.POINTER(MlpStage), vp, vp]
-        L.ihmr_opt_forward_verts.argtypes = [vp, C.POINTER(OptIO), i, vp]
-        L.ihmr_eval_metrics.argtypes = [vp, vp, vp, vp, vp, i, vp, vp]
-        L.ihmr_eval_mpvpe.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, vp, vp]
-        # a library named with IHMR_HIP_LIBRARY may be an older build (A/B runs against the parent commit): it loads, and a call of an
-        # entry point it lacks raises AttributeError
-        for name, sig in (("ihmr_eval_pa_joints", [vp, vp, vp, i, vp, vp, vp]), ("ihmr_eval_pa_verts", [vp, vp, vp, vp, vp, vp, i, vp, vp, vp]),
-                          ("ihmr_eval_curve_joints", [vp, vp, vp, i, vp, i, vp, vp]),
-                          ("ihmr_eval_curve_verts", [vp] * 7 + [i, vp, i, vp, i, vp, vp, vp, vp]),
-                          ("ihmr_eval_mrrpe", [vp, vp, vp, vp, i, vp, vp]),
-                          ("ihmr_eval_contact", [vp] * 7 + [i, vp, i, vp, vp, vp, vp]),
-                          ("ihmr_sdf_volume", [vp, vp, i, i, vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp]),
-                          ("ihmr_surface_distance", [vp, i, vp, i, vp, i, i, vp, i, i, vp, vp, vp, vp]),
-                          ("ihmr_surface_distance_bwd", [vp, i, vp, i, vp, i, i, vp, i, vp, vp, vp, vp, vp, vp, vp])):
-            if hasattr(L, name):
-                getattr(L, name).argtypes = sig
-        L.ihmr_graph_destroy.argtypes = [vp]
-        L.ihmr_conv_igemm.argtypes = [vp, vp, vp, vp, vp] + [i] * 16 + [vp, C.c_size_t, vp]
-        L.ihmr_maxpool3x3s2.argtypes = [vp, vp, i, i, i, i, i, i, vp]
-        L.ihmr_avgpool_relu.argtypes = [vp, vp, i, i, i, i, vp]
-        L.ihmr_conv_igemm_bf16.argtypes = [vp, vp, vp, vp, vp] + [i] * 16 + [vp, C.c_size_t, vp]
-        L.ihmr_pack_image_bf16.argtypes = [vp, vp, i, i, i, vp]
-        L.ihmr_maxpool3x3s2_bf16.argtypes = [vp, vp, i, i, i, i, i, i, vp]
-        L.ihmr_avgpool_relu_bf16.argtypes = [vp, vp, i, i, i, i, vp]
-        L.ihmr_cast_f32_bf16.argtypes = [vp, vp, C.c_size_t, vp]
-        L.ihmr_mlp_train_grad.argtypes = [vp, vp, C.POINTER(OptIO), i, C.POINTER(OptWeights), C.POINTER(TrainWeights)] + [vp] * 8 + [i, vp, i, vp]
-        L.ihmr_transpose.argtypes = [vp, vp, i, i, i, i, vp]
-        L.ihmr_relu_backward.argtypes = [vp, vp, i, i, i, i, vp]
-        L.ihmr_colsum.argtypes = [vp, vp, i, i, i, vp]
-        L.ihmr_adam_step.argtypes = [vp, vp, vp, vp, C.c_size_t, f, f, f, f, f, i, vp]
-        L.ihmr_bn_workspace_bytes.argtypes = [i]
-        L.ihmr_bn_workspace_bytes.restype = C.c_size_t
-        L.ihmr_bn_train_forward.argtypes = [vp, C.c_long, i, vp, vp, vp, i, f, vp, vp, vp, vp, vp, vp, f, vp, vp]
-        L.ihmr_bn_train_backward.argtypes = [vp, vp, C.c_long, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.ihmr_conv_wgrad.argtypes = [vp, vp, vp] + [i] * 14 + [vp, C.c_size_t, vp]
-        L.ihmr_dilate2.argtypes = [vp, vp, i, i, i, i, vp]
-        L.ihmr_interleave2.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp]
-        L.ihmr_pack_dgrad_weight.argtypes = [vp, vp, i, i, i, i, i, i, vp]
-        L.ihmr_maxpool3x3s2_backward.argtypes = [vp, vp, vp, i, i, i, i, i, i, vp]
-        L.ihmr_avgpool_relu_backward.argtypes = [vp, vp, vp, i, i, i, i, vp]
-        L.ihmr_preprocess_images.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp]
-        L.ihmr_augment_images.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, i, vp, vp, vp, vp, C.POINTER(C.c_int), vp]
-        L.ihmr_augment_labels.argtypes = [vp, vp, i, i] + [vp] * 14 + [vp]
-        L.ihmr_render_workspace_bytes.argtypes = [i, i]
-        L.ihmr_render_workspace_bytes.restype = C.c_size_t
-        L.ihmr_render_meshes.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp, C.POINTER(RenderLights), vp, i, vp, vp, vp, i, vp]
-        L.ihmr_draw_keypoints.argtypes = [vp, vp, vp, C.c_char_p, i, i, i, vp]
-        # (an older library named with IHMR_HIP_LIBRARY lacks these three: a call of them raises AttributeError)
-        for name, sig in (("ihmr_view_vertices", [vp, vp, i, i, vp, i, vp, vp, i, vp]),
-                          ("ihmr_heat_colours", [vp, vp, C.POINTER(f * 3), f, f, i, i, i, vp, i, vp]),
-                          ("ihmr_paint_meshes", [vp, vp, vp, vp, i, i, i, vp, vp, vp, C.POINTER(RenderLights), vp, i, vp, vp, vp, i, vp])):
-            if hasattr(L, name):
-                getattr(L, name).argtypes = sig
-        L.ihmr_opt_sdf_stats.argtypes = [vp, vp, C.POINTER(OptIO), i, C.POINTER(OptWeights), vp, vp]
-        L.ihmr_opt_sdf_counters.argtypes = [C.POINTER(OptIO), i, vp, i]
-        L.ihmr_opt_sdf_inside_bits.argtypes = [C.POINTER(OptIO), i, vp, vp]
-        L.ihmr_set_kernel_timer.argtypes = [C.POINTER(KernelTimer)]
-        L.ihmr_flush_kernel_timer.argtypes = []
-        L.ihmr_copy_segments.argtypes = [C.POINTER(CopySeg), i, vp]
-        L.ihmr_root_align_joints.argtypes = [vp, vp, i, vp]
-        L.ihmr_version.restype = C.c_char_p
-        _LIB = L
+        _LIB = bind(C.CDLL(_resolve_library()))
     return _LIB
 
 

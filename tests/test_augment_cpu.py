@@ -6,7 +6,6 @@ import ctypes
 import os
 import re
 import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -15,9 +14,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import augment_ref as A  # noqa: E402
+import hostbuild  # noqa: E402
 
-SAN = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off", "-fno-fast-math",
-       "-march=x86-64-v3"]
 GOLDEN = os.path.join(ROOT, "tests", "golden", "augment.npz")
 needs_gxx = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 
@@ -25,19 +23,17 @@ needs_gxx = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not avai
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("augment")
-    exe = str(d / "augment_host_driver")
-    subprocess.check_call(["g++"] + SAN + [os.path.join(ROOT, "tests", "augment_host_driver.cpp"), "-o", exe])
+    exe = hostbuild.build("augment_host_driver.cpp", d, hostbuild.X86_V3)
 
     def run(op, payload=None, dtype=np.uint8):
         fout = str(d / f"{op}.out")
-        args = [exe, op]
+        args = [op]
         if payload is not None:
             fin = str(d / f"{op}.in")
             with open(fin, "wb") as fh:
                 fh.write(payload)
             args.append(fin)
-        r = subprocess.run(args + [fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-        assert r.returncode == 0, r.stderr[-3000:]            # a sanitizer report is a non-zero exit
+        hostbuild.run(exe, *args, fout)
         return np.fromfile(fout, dtype)
     return run
 
@@ -215,11 +211,5 @@ def test_header_binding_and_library_agree_on_the_new_entry_points():
     kinds = dict(double="f8", float="f4", int32_t="i4")
     assert all(G.PARAMS_DTYPE[n].base == np.dtype(kinds[t]) for t, n in fields)
     if shutil.which("g++") is not None:                                       # sizeof / offsetof as the compiler lays the struct out
-        src = '#include <stddef.h>\n#include <stdio.h>\n#include "ihmr_hip.h"\nint main(){printf("%zu", sizeof(ihmr_aug_params));' + \
-            "".join(f'printf(" %zu", offsetof(ihmr_aug_params, {n}));' for n in G.PARAMS_DTYPE.names) + "return 0;}"
-        import tempfile
-        with tempfile.TemporaryDirectory() as d:
-            open(os.path.join(d, "s.cpp"), "w").write(src)
-            subprocess.check_call(["g++", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.cpp"), "-o", os.path.join(d, "s")])
-            vals = [int(x) for x in subprocess.check_output([os.path.join(d, "s")], text=True).split()]
-        assert vals[0] == G.PARAMS_DTYPE.itemsize and vals[1:] == [G.PARAMS_DTYPE.fields[n][1] for n in G.PARAMS_DTYPE.names]
+        size, offsets = hostbuild.struct_layouts({"ihmr_aug_params": G.PARAMS_DTYPE.names})["ihmr_aug_params"]
+        assert size == G.PARAMS_DTYPE.itemsize and offsets == {n: G.PARAMS_DTYPE.fields[n][1] for n in G.PARAMS_DTYPE.names}

@@ -14,6 +14,8 @@ import subprocess
 
 import pytest
 
+import codeobj
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "ihmr_amd", "csrc")
 BASE = ["hipcc", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}", "--cuda-device-only"]
@@ -33,29 +35,18 @@ def test_instrumentation_macros_compile(macro):
     assert r.returncode == 0 and not errs, (macro, r.stderr[-3000:])
 
 
-def test_loop_collision_kernels_do_not_spill(tmp_path):
+def test_loop_collision_kernels_do_not_spill():
     """Device assembly of the product build: the kernels the refinement loop launches at its register budgets -- both forms of
     sdf_prep_kernel (64 registers) and sdf_dist_kernel (128) -- use no scratch at all (`.private_segment_fixed_size` 0, no spilled
     vector register)."""
-    out = tmp_path / "ihmr.s"
-    r = subprocess.run(BASE + ["-O3", "-S", "-o", str(out), "ihmr_hip.hip"], cwd=SRC, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    text = out.read_text()
-    # the AMDGPU metadata block: one YAML record per kernel
-    recs = re.findall(r"\.name:\s+(\S+)(.*?)\.wavefront_size", text, flags=re.S)
-    seen = {}
-    for name, body in recs:
-        if not re.match(r"_Z15sdf_(prep|dist)_kernelILb0", name):
-            continue
-        get = lambda key: int(re.search(rf"\.{key}:\s+(\d+)", body).group(1))
-        seen[name] = (get("vgpr_count"), get("vgpr_spill_count"), get("private_segment_fixed_size"))
+    seen = {name: (r["vgpr_count"], r["vgpr_spill_count"], r["private_segment_fixed_size"])
+            for name, r in codeobj.records().items() if re.match(r"_Z15sdf_(prep|dist)_kernelILb0", name)}
     assert len(seen) >= 3, list(seen)
     # the staging wait of sdf_list_item (SDF_STAGE_CLOSE_KEEP1: `s_waitcnt vmcnt(1)` + barrier) is correct only while the wave's YOUNGEST
     # vector-memory operation at that point is the map-word prefetch -- a plain load issued after the table's LDS-DMA pieces -- and not
     # a DMA piece, a spill reload or a store (advisor, round 5): in the built code the nearest memory instruction before every such
     # wait must be that 8-byte global load
-    body = text[text.index("_Z15sdf_dist_kernelILb0EEv12SdfWorkspace:"):]
-    body = body[:body.index("s_endpgm")].splitlines()
+    body = codeobj.body("_Z15sdf_dist_kernelILb0EEv12SdfWorkspace")
     waits = [i for i, l in enumerate(body) if "s_waitcnt vmcnt(1)" in l and any("s_barrier" in x for x in body[i + 1:i + 6])]
     assert waits, "no vmcnt(1) staging wait found in sdf_dist_kernel"
     for i in waits:

@@ -6,7 +6,6 @@ and the build: both kernels without scratch memory, the LDS the header names, ev
 import os
 import pickle
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -14,12 +13,13 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import codeobj  # noqa: E402
 import contact_cases as CT  # noqa: E402
 import curve_cases as CC  # noqa: E402
+import hostbuild  # noqa: E402
 
 from ihmr_amd import evaluator as E  # noqa: E402
 
-SAN = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off", "-fno-fast-math"]
 TOL = CT.TOL
 
 
@@ -290,16 +290,14 @@ def test_six_wrong_rules_each_land_ten_times_beyond_the_bar():
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("contact")
-    exe = str(d / "contact_host_driver")
-    subprocess.check_call(["g++"] + SAN + [os.path.join(ROOT, "tests", "contact_host_driver.cpp"), "-o", exe])
+    exe = hostbuild.build("contact_host_driver.cpp", d)
     count = [0]
 
     def run(op, payload):
         count[0] += 1
         fin, fout = str(d / f"in{count[0]}.bin"), str(d / f"out{count[0]}.bin")
         np.ascontiguousarray(payload, np.float64).tofile(fin)
-        r = subprocess.run([exe, op, fin, fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-        assert r.returncode == 0, (r.returncode, r.stderr[-3000:])       # a sanitizer report is a non-zero exit
+        hostbuild.run(exe, op, fin, fout)
         return np.fromfile(fout, np.float64)
     return run
 
@@ -384,21 +382,15 @@ def test_contact_index_minimum_and_mrrpe_are_exact(driver):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the build
-def test_the_two_kernels_use_no_scratch_and_the_lds_the_header_names(tmp_path):
+def test_the_two_kernels_use_no_scratch_and_the_lds_the_header_names():
     import ctypes
 
     from ihmr_amd import hip
-    out = tmp_path / "ihmr.s"
-    cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-           "--cuda-device-only", "-S", "-o", str(out), "ihmr_hip.hip"]
-    r = subprocess.run(cmd, cwd=os.path.join(ROOT, "ihmr_amd", "csrc"), capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
     seen = {}
-    for body in re.findall(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", out.read_text(), flags=re.S):
-        name = re.search(r"\.name:\s+(\S+)", body).group(1)
+    for name, rec in codeobj.records().items():
         for k in ("eval_mrrpe_kernel", "eval_contact_kernel"):
             if k in name:
-                seen[k] = {key: int(re.search(rf"\.{key}:\s+(\d+)", body).group(1)) for key in
+                seen[k] = {key: rec[key] for key in
                            ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")}
     assert sorted(seen) == ["eval_contact_kernel", "eval_mrrpe_kernel"], sorted(seen)
     for name, m in sorted(seen.items()):

@@ -3,9 +3,7 @@ instruction present, no spills), the C ABI, the weight packing, the rounding hel
 CPU emulation of the numerics contract (tests/bf16_emulation.py) against the reference's own outputs."""
 import ctypes
 import os
-import re
 import shutil
-import subprocess
 import sys
 import types
 
@@ -14,47 +12,35 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "ihmr_amd", "csrc")
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-BASE = ["hipcc", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}", "--cuda-device-only"]
-SAN = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off", "-fno-fast-math",
-       "-march=x86-64-v3"]
+import codeobj  # noqa: E402
+import hostbuild  # noqa: E402
+
 NEW_SYMBOLS = ["ihmr_conv_igemm_bf16", "ihmr_pack_image_bf16", "ihmr_maxpool3x3s2_bf16", "ihmr_avgpool_relu_bf16", "ihmr_cast_f32_bf16"]
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not available")
-def test_bf16_conv_kernel_uses_the_bf16_matrix_cores_and_does_not_spill(tmp_path):
+def test_bf16_conv_kernel_uses_the_bf16_matrix_cores_and_does_not_spill():
     """Device assembly of the product build (as tests/test_build_cpu.py reads it): `conv_igemm_bf16_kernel` is instantiated, the code
     object holds a bf16 matrix instruction, and no instantiation of the kernel uses scratch."""
-    out = tmp_path / "ihmr.s"
-    r = subprocess.run(BASE + ["-O3", "-S", "-o", str(out), "ihmr_hip.hip"], cwd=SRC, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    text = out.read_text()
-    recs = re.findall(r"\.name:\s+(\S+)(.*?)\.wavefront_size", text, flags=re.S)
-    seen = {}
-    for name, body in recs:
-        if "conv_igemm_bf16_kernel" not in name:
-            continue
-        get = lambda key: int(re.search(rf"\.{key}:\s+(\d+)", body).group(1))
-        seen[name] = (get("vgpr_count"), get("vgpr_spill_count"), get("private_segment_fixed_size"))
+    seen = {name: (r["vgpr_count"], r["vgpr_spill_count"], r["private_segment_fixed_size"])
+            for name, r in codeobj.records().items() if "conv_igemm_bf16_kernel" in name}
     assert seen, "no conv_igemm_bf16_kernel instantiation in the code object"
     for name, (vgpr, spill, scratch) in seen.items():
         print(f"[build] {name}: {vgpr} VGPRs, {spill} spilled, {scratch} B scratch")
         assert spill == 0 and scratch == 0, (name, vgpr, spill, scratch)
         # the kernel's own body issues the bf16 matrix instruction
-        body = text[text.index(name + ":"):]
-        body = body[:body.index("s_endpgm")]
+        body = "\n".join(codeobj.body(name))
         assert "v_mfma_f32_32x32x16_bf16" in body or "v_mfma_f32_16x16x32_bf16" in body, name
 
 
 def test_library_exports_the_bf16_entry_points():
     """The five new symbols resolve in the built library (it loads without a GPU) and the version string says 0.2."""
     from ihmr_amd import hip
-    L = ctypes.CDLL(hip.build())
+    L = hip.bind(ctypes.CDLL(hip.build()))
     for sym in NEW_SYMBOLS:
         assert hasattr(L, sym), sym
         assert sym in hip.EXPORTED_SYMBOLS, sym
-    L.ihmr_version.restype = ctypes.c_char_p
     assert b"0.2" in L.ihmr_version() and b"gfx950" in L.ihmr_version()
 
 
@@ -103,8 +89,7 @@ def test_rounding_helper_has_the_bits_of_torch(tmp_path):
     """`ihmr_f32_to_bf16` / `ihmr_bf16_to_f32` of csrc/ihmr_pure.h on the host under AddressSanitizer / UBSan: all 65 536 bf16 patterns
     widen exactly and round-trip (NaNs to the quiet NaN torch gives), every tie with even and odd neighbours, +-0, subnormals, the
     largest finite float (rounds to inf), +-inf, NaNs; bits equal `torch.tensor(x).bfloat16()`."""
-    exe = str(tmp_path / "pure_bf16_driver")
-    subprocess.check_call(["g++"] + SAN + [os.path.join(ROOT, "tests", "pure_bf16_driver.cpp"), "-o", exe])
+    exe = hostbuild.build("pure_bf16_driver.cpp", tmp_path, hostbuild.X86_V3)
 
     def run(op, words, out_dtype):
         words = np.ascontiguousarray(words, np.uint32)
@@ -112,8 +97,7 @@ def test_rounding_helper_has_the_bits_of_torch(tmp_path):
         with open(fin, "wb") as fh:
             fh.write(np.int32(words.size).tobytes())
             fh.write(words.tobytes())
-        r = subprocess.run([exe, op, fin, fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-        assert r.returncode == 0, r.stderr[-3000:]
+        hostbuild.run(exe, op, fin, fout)
         return np.fromfile(fout, out_dtype)
 
     def torch_bits(words):

@@ -16,7 +16,6 @@ Every case runs twice on fresh instances (a captured graph keeps the switch it w
   (`ihmr_opt_sdf_inside_bits`) after each stage, and the work counters -- `ray_tests`, `needed_voxels`, `inside_voxels` and the rest:
   the two paths must do the same work, not only reach the same result;
 * one dense-grid call (`sdf_prep_kernel<true, 512>`) on the deep batch, the grid compared bit for bit."""
-import ctypes as C
 import types
 
 import numpy as np
@@ -54,9 +53,7 @@ class _Switch:
 
     def __enter__(self):
         from ihmr_amd import hip
-        L = hip.lib()
-        L.ihmr_debug_prep_global_faces.argtypes, L.ihmr_debug_prep_global_faces.restype = [C.c_int], C.c_int
-        self.prev = L.ihmr_debug_prep_global_faces(1 if self.force else 0)
+        self.prev = hip.lib().ihmr_debug_prep_global_faces(1 if self.force else 0)
 
     def __exit__(self, *exc):
         from ihmr_amd import hip

@@ -6,7 +6,6 @@ restatements stay the independent oracle; this file is what ties them to the C++
 not only at the shapes and the one device the GPU tests run on.  A threshold edited on either side fails here, without a GPU."""
 import os
 import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -15,11 +14,9 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import encoder_shapes as E  # noqa: E402
 import encoder_train_shapes as T  # noqa: E402
+import hostbuild  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-SAN = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off", "-fno-fast-math",
-       "-march=x86-64-v3"]
 
 BATCHES = (1, 7, 64, 128, 512)
 CUS = (3, 120, 256, 304)
@@ -34,8 +31,7 @@ SWEEP = 3000
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("plan")
-    exe = str(d / "launch_plan_driver")
-    subprocess.check_call(["g++"] + SAN + [os.path.join(ROOT, "tests", "launch_plan_driver.cpp"), "-o", exe])
+    exe = hostbuild.build("launch_plan_driver.cpp", d, hostbuild.X86_V3)
 
     def run(op, records):
         records = np.ascontiguousarray(records, np.int64)
@@ -44,8 +40,7 @@ def driver(tmp_path_factory):
         with open(fin, "wb") as fh:
             fh.write(np.int64(records.shape[0]).tobytes())
             fh.write(records.tobytes())
-        r = subprocess.run([exe, op, fin, fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-        assert r.returncode == 0, r.stderr[-3000:]            # a sanitizer report is a non-zero exit
+        hostbuild.run(exe, op, fin, fout)
         return np.fromfile(fout, np.int64).reshape(records.shape[0], -1)
     return run
 
@@ -291,5 +286,5 @@ def test_plan_bn_chunks_equals_bn_rows_per_chunk(driver):
     got = driver("bn", [[M] for M in Ms])
     for M, (rows_per, chunks) in zip(Ms, got.tolist()):
         assert rows_per == _bn_rows_per_chunk(M) and chunks == _cdiv(M, rows_per) and 1 <= chunks <= 1024, (M, rows_per, chunks)
-    with open(os.path.join(ROOT, "ihmr_amd", "csrc", "launch_plan.h")) as fh:
+    with open(os.path.join(hostbuild.ROOT, "ihmr_amd", "csrc", "launch_plan.h")) as fh:
         assert "#define BN_MAX_CHUNKS 1024\n" in fh.read()                      # the 1024 of ihmr_bn_workspace_bytes

@@ -5,7 +5,6 @@ cut into single-joint segments by their invariants, the three refusals.  A wrong
 without a GPU; every comparison is exact."""
 import os
 import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -13,7 +12,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mano_cases as MC  # noqa: E402
-from test_launch_plan_cpu import ROOT, SAN  # noqa: E402
+import hostbuild  # noqa: E402
 
 pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 
@@ -30,8 +29,7 @@ OUT_ORDER = (("v_template", "f4"), ("shapedirs_t", "f4"), ("posedirs", "f4"), ("
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("mano_tables")
-    exe = str(d / "mano_tables_driver")
-    subprocess.check_call(["g++"] + SAN + [os.path.join(ROOT, "tests", "mano_tables_driver.cpp"), "-o", exe])
+    exe = hostbuild.build("mano_tables_driver.cpp", d, hostbuild.X86_V3)
     count = [0]
 
     def run(asset, second_shapedirs=None):
@@ -45,8 +43,7 @@ def driver(tmp_path_factory):
             if second_shapedirs is not None:
                 fh.write(np.ascontiguousarray(second_shapedirs, np.float32).tobytes())
         op = "build" if second_shapedirs is None else "update"
-        r = subprocess.run([exe, op, fin, fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-        assert r.returncode == 0 and not r.stderr, r.stderr[-3000:]          # a sanitizer report is a non-zero exit
+        assert not hostbuild.run(exe, op, fin, fout).stderr
         raw = open(fout, "rb").read()
         out = {"rc": int(np.frombuffer(raw, np.int32, 1)[0])}
         if out["rc"]:

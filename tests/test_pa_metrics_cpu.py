@@ -5,7 +5,6 @@ build: both kernels without scratch memory, every declared symbol exported."""
 import os
 import re
 import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -15,11 +14,12 @@ import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import codeobj  # noqa: E402
+import hostbuild  # noqa: E402
 import pa_cases as PC  # noqa: E402
 
 from ihmr_amd import evaluator as E  # noqa: E402
 
-SAN = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off", "-fno-fast-math"]
 TOL = 1e-9          # [m] the float64 route; the float32 route of the reference is held to 1e-7 like tests/golden/metrics.npz
 
 
@@ -130,16 +130,14 @@ def test_set_rules():
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("eval_pure")
-    exe = str(d / "eval_pure_driver")
-    subprocess.check_call(["g++"] + SAN + [os.path.join(ROOT, "tests", "eval_pure_driver.cpp"), "-o", exe])
+    exe = hostbuild.build("eval_pure_driver.cpp", d)
     count = [0]
 
     def run(op, payload):
         count[0] += 1
         fin, fout = str(d / f"in{count[0]}.bin"), str(d / f"out{count[0]}.bin")
         np.ascontiguousarray(payload, np.float64).tofile(fin)
-        r = subprocess.run([exe, op, fin, fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-        assert r.returncode == 0, r.stderr[-3000:]            # a sanitizer report is a non-zero exit
+        hostbuild.run(exe, op, fin, fout)
         return np.fromfile(fout, np.float64)
     return run
 
@@ -275,7 +273,7 @@ def test_evaluator_records_sums_and_properties():
     assert np.array_equal(on.pa_metric_sums(), np.zeros(6))
 
 
-def test_default_evaluator_pickles_as_before(tmp_path):
+def test_default_evaluator_pickles_as_before():
     """pa_metrics off: the records, the nine sums and a pickled evaluator's records carry nothing new."""
     import pickle
     ev = E.Evaluator(_mano())
@@ -341,17 +339,11 @@ def test_pa_kernels_use_no_scratch_and_the_header_is_exported(tmp_path):
     import ctypes
 
     from ihmr_amd import hip
-    out = tmp_path / "ihmr.s"
-    cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-           "--cuda-device-only", "-S", "-o", str(out), "ihmr_hip.hip"]
-    r = subprocess.run(cmd, cwd=os.path.join(ROOT, "ihmr_amd", "csrc"), capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
     seen = {}
-    for body in re.findall(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", out.read_text(), flags=re.S):
-        name = re.search(r"\.name:\s+(\S+)", body).group(1)
+    for name, rec in codeobj.records().items():
         for k in ("eval_pa_joints_kernel", "eval_pa_verts_kernel"):
             if k in name:
-                seen[k] = {key: int(re.search(rf"\.{key}:\s+(\d+)", body).group(1)) for key in
+                seen[k] = {key: rec[key] for key in
                            ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")}
     assert sorted(seen) == ["eval_pa_joints_kernel", "eval_pa_verts_kernel"], sorted(seen)
     for name, m in sorted(seen.items()):

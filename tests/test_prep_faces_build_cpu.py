@@ -7,16 +7,11 @@ register, vector or scalar.  The 1024-thread form runs two workgroups per CU: no
 
 The DMA that fills the table is tracked by the issuing wave's vmcnt only: in the built code every form waits `s_waitcnt vmcnt(0)`
 directly in front of the workgroup barrier that precedes the pair loop."""
-import os
-import re
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "ihmr_amd", "csrc")
-BASE = ["hipcc", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}", "--cuda-device-only"]
+import codeobj
 
 pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not available")
 
@@ -24,33 +19,9 @@ LDS_PER_CU = 163840
 FORMS = {"dense-512": "_Z15sdf_prep_kernelILb1ELi512E", "sparse-512": "_Z15sdf_prep_kernelILb0ELi512E", "sparse-1024": "_Z15sdf_prep_kernelILb0ELi1024E"}
 
 
-@pytest.fixture(scope="module")
-def assembly(tmp_path_factory):
-    out = tmp_path_factory.mktemp("prep_faces") / "ihmr.s"
-    r = subprocess.run(BASE + ["-O3", "-S", "-o", str(out), "ihmr_hip.hip"], cwd=SRC, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return out.read_text()
-
-
-def _records(text):
-    """The AMDGPU metadata block: one YAML record per kernel (a list item at two spaces; `.name` sits in the middle of its keys)."""
-    meta = text[text.index("amdhsa.kernels:"):]
-    recs = {}
-    for rec in re.split(r"^  - (?=\.)", meta, flags=re.M)[1:]:
-        name = re.search(r"^\s+\.name:\s+(\S+)", rec, flags=re.M).group(1)
-        recs[name] = {k: int(v) for k, v in re.findall(r"^\s{4}\.(\w+):\s+(\d+)\s*$", rec, flags=re.M)}
-    return recs
-
-
-def _form(recs, prefix):
-    hits = [(n, r) for n, r in recs.items() if n.startswith(prefix)]
-    assert len(hits) == 1, [n for n, _ in hits]
-    return hits[0]
-
-
 @pytest.mark.parametrize("form", ["dense-512", "sparse-512"])
-def test_512_thread_forms_fit_four_workgroups_per_cu(assembly, form):
-    name, r = _form(_records(assembly), FORMS[form])
+def test_512_thread_forms_fit_four_workgroups_per_cu(form):
+    name, r = codeobj.kernel(FORMS[form])
     print(f"[build] {name[:48]}: {r['vgpr_count']} VGPRs ({r['vgpr_spill_count']} spilled), {r['sgpr_count']} SGPRs ({r['sgpr_spill_count']} spilled), "
           f"{r['private_segment_fixed_size']} B scratch, {r['group_segment_fixed_size']} B LDS")
     assert r["vgpr_count"] <= 64, r
@@ -59,8 +30,8 @@ def test_512_thread_forms_fit_four_workgroups_per_cu(assembly, form):
     assert r["group_segment_fixed_size"] <= 40960 and 4 * r["group_segment_fixed_size"] <= LDS_PER_CU, r
 
 
-def test_1024_thread_form_fits_two_workgroups_per_cu(assembly):
-    name, r = _form(_records(assembly), FORMS["sparse-1024"])
+def test_1024_thread_form_fits_two_workgroups_per_cu():
+    name, r = codeobj.kernel(FORMS["sparse-1024"])
     print(f"[build] {name[:48]}: {r['vgpr_count']} VGPRs ({r['vgpr_spill_count']} spilled), {r['private_segment_fixed_size']} B scratch, "
           f"{r['group_segment_fixed_size']} B LDS")
     assert r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0, r
@@ -68,12 +39,11 @@ def test_1024_thread_form_fits_two_workgroups_per_cu(assembly):
 
 
 @pytest.mark.parametrize("form", sorted(FORMS))
-def test_face_table_dma_is_waited_for_at_the_barrier_before_the_pair_loop(assembly, form):
+def test_face_table_dma_is_waited_for_at_the_barrier_before_the_pair_loop(form):
     """The pair loop is the kernel's only LDS XOR (`atomicXor(&parity[col], hits)`); the barrier in front of it is the one that
     publishes the queued pairs."""
-    name, _ = _form(_records(assembly), FORMS[form])
-    body = assembly[assembly.index(f"\n{name}:"):]
-    body = body[:body.index("s_endpgm")].splitlines()
+    name, _ = codeobj.kernel(FORMS[form])
+    body = codeobj.body(name)
     dma = [i for i, l in enumerate(body) if "global_load_lds_dwordx4" in l]
     assert dma, "no LDS-DMA load in the kernel: the face table is not staged"
     xor = [i for i, l in enumerate(body) if "ds_xor_b32" in l]

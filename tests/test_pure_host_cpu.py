@@ -14,17 +14,16 @@ import numpy as np
 import pytest
 import torch
 
+import hostbuild
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-SAN = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off", "-fno-fast-math",
-       "-march=x86-64-v3"]
 
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("pure")
-    exe = str(d / "pure_host_driver")
-    subprocess.check_call(["g++"] + SAN + [os.path.join(ROOT, "tests", "pure_host_driver.cpp"), "-o", exe])
+    exe = hostbuild.build("pure_host_driver.cpp", d, hostbuild.X86_V3)
 
     def run(op, records, out_dtype=np.float32):
         records = np.ascontiguousarray(records, np.float32)
@@ -32,8 +31,7 @@ def driver(tmp_path_factory):
         with open(fin, "wb") as fh:
             fh.write(np.int32(records.shape[0]).tobytes())
             fh.write(records.tobytes())
-        r = subprocess.run([exe, op, fin, fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-        assert r.returncode == 0, r.stderr[-3000:]            # a sanitizer report is a non-zero exit
+        hostbuild.run(exe, op, fin, fout)
         return np.fromfile(fout, out_dtype).reshape(records.shape[0], -1)
     return run
 

@@ -6,7 +6,6 @@ import ctypes
 import os
 import re
 import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -15,9 +14,10 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import render_cases as RC  # noqa: E402
+import codeobj  # noqa: E402
+import hostbuild  # noqa: E402
 import render_ref as R  # noqa: E402
 
-SAN = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off", "-fno-fast-math"]
 needs_gxx = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 needs_hipcc = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not available")
 f32 = np.float32
@@ -33,41 +33,30 @@ def test_header_binding_and_library_agree_on_the_render_entry_points():
     assert declared <= set(hip.EXPORTED_SYMBOLS)
     assert ctypes.sizeof(hip.RenderLights) == 72
     if shutil.which("hipcc") is not None:
-        L = ctypes.CDLL(hip.build())
+        L = hip.bind(ctypes.CDLL(hip.build()))
         for sym in declared:
             assert hasattr(L, sym), sym
-        L.ihmr_render_workspace_bytes.restype = ctypes.c_size_t
         assert L.ihmr_render_workspace_bytes(3, 1556) == 3 * 1556 * 24 and L.ihmr_render_workspace_bytes(0, 1556) == 0
         # bad shapes and missing pointers are refused before anything is launched (no GPU is touched here)
-        vp = ctypes.c_void_p
-        L.ihmr_render_meshes.argtypes = [vp] * 4 + [ctypes.c_int] * 3 + [vp] * 5 + [ctypes.c_int] + [vp] * 3 + [ctypes.c_int, vp]
         lights = hip.RenderLights()
         one = ctypes.c_void_p(64)
-        good = [one, one, one, one, 1556, 3076, 1538, None, one, one, ctypes.addressof(lights), None, 64, one, None, one, 1, None]
+        good = [one, one, one, one, 1556, 3076, 1538, None, one, one, ctypes.byref(lights), None, 64, one, None, one, 1, None]
         for at, bad in ((0, None), (1, None), (8, None), (10, None), (13, None), (15, None), (4, 0), (5, 0), (6, 3077), (12, 15), (12, 2049), (16, 0)):
             args = list(good)
             args[at] = bad
             assert L.ihmr_render_meshes(*args) == -1, (at, bad)
-        L.ihmr_draw_keypoints.argtypes = [vp, vp, vp, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
         assert L.ihmr_draw_keypoints(None, one, one, b"\0\0\0", 1, 64, 42, None) == -1
         assert L.ihmr_draw_keypoints(one, one, one, b"\0\0\0", 1, 64, 0, None) == -1
 
 
 @needs_hipcc
-def test_render_kernels_use_no_scratch(tmp_path):
+def test_render_kernels_use_no_scratch():
     """The z-buffer, the face record a thread sets up and the four pixels' winners live in registers: a spill would put them in memory."""
-    out = tmp_path / "ihmr.s"
-    cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-           "--cuda-device-only", "-S", "-o", str(out), "ihmr_hip.hip"]
-    r = subprocess.run(cmd, cwd=os.path.join(ROOT, "ihmr_amd", "csrc"), capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    recs = re.findall(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", out.read_text(), flags=re.S)
     seen = {}
-    for body in recs:
-        name = re.search(r"\.name:\s+(\S+)", body).group(1)
+    for name, rec in codeobj.records().items():
         for k in ("render_vertex_kernel", "render_raster_kernel", "draw_keypoints_kernel"):
             if k in name:
-                seen[k] = {key: int(re.search(rf"\.{key}:\s+(\d+)", body).group(1)) for key in
+                seen[k] = {key: rec[key] for key in
                            ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")}
     assert sorted(seen) == ["draw_keypoints_kernel", "render_raster_kernel", "render_vertex_kernel"], sorted(seen)
     for name, m in sorted(seen.items()):
@@ -81,8 +70,7 @@ def test_render_kernels_use_no_scratch(tmp_path):
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("render")
-    exe = str(d / "render_host_driver")
-    subprocess.check_call(["g++"] + SAN + [os.path.join(ROOT, "tests", "render_host_driver.cpp"), "-o", exe])
+    exe = hostbuild.build("render_host_driver.cpp", d)
     count = [0]
 
     def run(op, payload):
@@ -90,8 +78,7 @@ def driver(tmp_path_factory):
         fin, fout = str(d / f"in{count[0]}.bin"), str(d / f"out{count[0]}.bin")
         with open(fin, "wb") as fh:
             fh.write(payload)
-        r = subprocess.run([exe, op, fin, fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-        assert r.returncode == 0, r.stderr[-3000:]            # a sanitizer report is a non-zero exit
+        hostbuild.run(exe, op, fin, fout)
         return open(fout, "rb").read()
 
     def render(verts, faces, cam, S, albedo, split, present=(1, 1), bg=None, light=None):

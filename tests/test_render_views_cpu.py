@@ -6,7 +6,6 @@ import ctypes
 import os
 import re
 import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -14,11 +13,12 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import codeobj  # noqa: E402
+import hostbuild  # noqa: E402
 import render_cases as RC  # noqa: E402
 import render_ref as R  # noqa: E402
 import render_views_ref as V  # noqa: E402
 
-SAN = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off", "-fno-fast-math"]
 needs_gxx = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 needs_hipcc = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not available")
 f32 = np.float32
@@ -42,13 +42,11 @@ def test_header_binding_and_library_agree_on_the_view_entry_points():
         assert hip.EXPORTED_SYMBOLS.count(sym) == 1, sym
     if shutil.which("hipcc") is None:
         return
-    L = ctypes.CDLL(hip.build())
+    L = hip.bind(ctypes.CDLL(hip.build()))
     for sym in NEW:
         assert hasattr(L, sym), sym
     # bad shapes, missing pointers and overlapping buffers are refused before anything is launched (no GPU is touched here)
-    vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     one = ctypes.c_void_p(1 << 20)
-    L.ihmr_view_vertices.argtypes = [vp, vp, i, i, vp, i, vp, vp, i, vp]
     nbytes = 2 * 1556 * 12
     far = ctypes.c_void_p((1 << 20) + nbytes)                                    # the first byte behind `verts`: no overlap
     good = [one, None, 1556, 778, one, 0, None, far, 2, None]
@@ -57,8 +55,7 @@ def test_header_binding_and_library_agree_on_the_view_entry_points():
         args = list(good)
         args[at] = bad
         assert L.ihmr_view_vertices(*args) == -1, (at, bad)
-    L.ihmr_heat_colours.argtypes = [vp, vp, ctypes.POINTER(f * 3), f, f, i, i, i, vp, i, vp]
-    hot = (f * 3)(0, 0, 1)
+    hot = (ctypes.c_float * 3)(0, 0, 1)
     good = [one, one, hot, 0.0, 0.005, 1556, 778, 1, one, 2, None]
     for at, bad in ((0, None), (1, None), (2, None), (8, None), (4, 0.0), (4, -1.0), (3, 0.005), (3, float("nan")), (4, float("nan")),
                     (4, float("inf")), (3, float("-inf")), (5, 0), (5, 1555), (5, 1557), (6, 777), (6, -1), (7, 2), (7, -1), (9, 0), (9, 65536)):
@@ -68,9 +65,8 @@ def test_header_binding_and_library_agree_on_the_view_entry_points():
     args = list(good)
     args[5], args[6], args[7] = 1555, 1556, 0                                    # n_split beyond n_verts, also under layout 0
     assert L.ihmr_heat_colours(*args) == -1
-    L.ihmr_paint_meshes.argtypes = [vp] * 4 + [i] * 3 + [vp] * 5 + [i] + [vp] * 3 + [i, vp]
     lights = hip.RenderLights()
-    good = [one, one, one, one, 1556, 3076, 1538, None, one, one, ctypes.addressof(lights), None, 64, one, None, one, 1, None]
+    good = [one, one, one, one, 1556, 3076, 1538, None, one, one, ctypes.byref(lights), None, 64, one, None, one, 1, None]
     for at, bad in ((0, None), (1, None), (8, None), (10, None), (13, None), (15, None), (4, 0), (5, 0), (6, 3077), (12, 15), (12, 2049), (16, 0)):
         args = list(good)
         args[at] = bad
@@ -78,24 +74,17 @@ def test_header_binding_and_library_agree_on_the_view_entry_points():
 
 
 @needs_hipcc
-def test_view_kernels_use_no_scratch_and_the_render_kernels_keep_their_budget(tmp_path):
+def test_view_kernels_use_no_scratch_and_the_render_kernels_keep_their_budget():
     """The three new kernels spill nothing and have no private segment; the three kernels of the plain render keep the registers, the
     LDS and the empty private segment they had before the vertex stage became a function two kernels call."""
-    out = tmp_path / "ihmr.s"
-    cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-           "--cuda-device-only", "-S", "-o", str(out), "ihmr_hip.hip"]
-    r = subprocess.run(cmd, cwd=os.path.join(ROOT, "ihmr_amd", "csrc"), capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    recs = re.findall(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", out.read_text(), flags=re.S)
     names = ("render_vertex_kernel", "render_raster_kernel", "draw_keypoints_kernel", "paint_vertex_kernel", "view_vertices_kernel",
              "heat_colours_kernel")
     seen = {}
-    for body in recs:
-        name = re.search(r"\.name:\s+(\S+)", body).group(1)
+    for name, rec in codeobj.records().items():
         for k in names:
             if k in name:
                 assert k not in seen, name
-                seen[k] = {key: int(re.search(rf"\.{key}:\s+(\d+)", body).group(1)) for key in
+                seen[k] = {key: rec[key] for key in
                            ("vgpr_count", "agpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")}
     assert sorted(seen) == sorted(names), sorted(seen)
     for name, m in sorted(seen.items()):
@@ -114,8 +103,7 @@ def test_view_kernels_use_no_scratch_and_the_render_kernels_keep_their_budget(tm
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("views")
-    exe = str(d / "view_host_driver")
-    subprocess.check_call(["g++"] + SAN + [os.path.join(ROOT, "tests", "view_host_driver.cpp"), "-o", exe])
+    exe = hostbuild.build("view_host_driver.cpp", d)
     count = [0]
 
     def run(op, payload, ok=True):
@@ -123,8 +111,7 @@ def driver(tmp_path_factory):
         fin, fout = str(d / f"in{count[0]}.bin"), str(d / f"out{count[0]}.bin")
         with open(fin, "wb") as fh:
             fh.write(payload)
-        r = subprocess.run([exe, op, fin, fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-        assert (r.returncode == 0) == ok, r.stderr[-3000:]            # a sanitizer report is a non-zero exit
+        hostbuild.run(exe, op, fin, fout, ok=ok)
         return open(fout, "rb").read()
 
     class D:

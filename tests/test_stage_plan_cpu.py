@@ -7,7 +7,6 @@ import itertools
 import math
 import os
 import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -15,7 +14,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import stage_cases as sc  # noqa: E402
-from test_launch_plan_cpu import ROOT, SAN  # noqa: E402
+import hostbuild  # noqa: E402
 
 pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 
@@ -38,8 +37,7 @@ ITERS = tuple((it, n) for n in range(1, 5) for it in range(n))
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("stage_plan")
-    exe = str(d / "stage_plan_driver")
-    subprocess.check_call(["g++"] + SAN + [os.path.join(ROOT, "tests", "stage_plan_driver.cpp"), "-o", exe])
+    exe = hostbuild.build("stage_plan_driver.cpp", d, hostbuild.X86_V3)
 
     def run(op, records):
         records = np.ascontiguousarray(records, np.float64)
@@ -48,8 +46,7 @@ def driver(tmp_path_factory):
         with open(fin, "wb") as fh:
             fh.write(np.int64(records.shape[0]).tobytes())
             fh.write(records.tobytes())
-        r = subprocess.run([exe, op, fin, fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-        assert r.returncode == 0, r.stderr[-3000:]            # a sanitizer report is a non-zero exit
+        hostbuild.run(exe, op, fin, fout)
         return np.fromfile(fout, np.float64).reshape(records.shape[0], -1)
     return run
 

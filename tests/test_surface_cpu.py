@@ -7,7 +7,6 @@ exported."""
 import os
 import pickle
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -15,12 +14,13 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import codeobj  # noqa: E402
 import curve_cases as CC  # noqa: E402
+import hostbuild  # noqa: E402
 import surface_ref as SR  # noqa: E402
 
 from ihmr_amd import evaluator as E  # noqa: E402
 
-SAN = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off", "-fno-fast-math"]
 DIST_TOL, BARY_TOL = 1e-12, 1e-9            # the driver's distance [m] and weights against the statement
 
 
@@ -143,8 +143,7 @@ def test_gradient_is_zero_on_the_surface_and_for_a_nan():
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("surface")
-    exe = str(d / "surface_host_driver")
-    subprocess.check_call(["g++"] + SAN + [os.path.join(ROOT, "tests", "surface_host_driver.cpp"), "-o", exe])
+    exe = hostbuild.build("surface_host_driver.cpp", d)
     count = [0]
 
     def run(c, g=None, signed=1, F_dist=None):
@@ -155,8 +154,7 @@ def driver(tmp_path_factory):
         with open(fin, "wb") as fh:
             for a in (np.array([P, V, F_total, fd if F_dist is None else F_dist, signed], np.int32), c.points, c.verts, c.faces, np.asarray(g, np.float64)):
                 fh.write(np.ascontiguousarray(a).tobytes())
-        r = subprocess.run([exe, fin, fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-        assert r.returncode == 0, (r.returncode, r.stderr[-3000:])       # a sanitizer report is a non-zero exit
+        hostbuild.run(exe, fin, fout)
         out = np.fromfile(fout, np.float64)
         cut = np.cumsum([P, P, 3 * P, 3 * P, 3 * V])
         assert len(out) == cut[-1]
@@ -308,21 +306,15 @@ def test_surface_sums_add_over_split_batches_and_give_the_metrics(K):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the build
-def test_the_two_kernels_use_no_scratch_and_the_lds_the_header_names(tmp_path):
+def test_the_two_kernels_use_no_scratch_and_the_lds_the_header_names():
     import ctypes
 
     from ihmr_amd import hip
-    out = tmp_path / "ihmr.s"
-    cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-           "--cuda-device-only", "-S", "-o", str(out), "ihmr_hip.hip"]
-    r = subprocess.run(cmd, cwd=os.path.join(ROOT, "ihmr_amd", "csrc"), capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
     seen = {}
-    for body in re.findall(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", out.read_text(), flags=re.S):
-        name = re.search(r"\.name:\s+(\S+)", body).group(1)
+    for name, rec in codeobj.records().items():
         for k in ("surface_dist_kernel", "surface_dist_bwd_kernel"):
             if k + "PK" in name:
-                seen[k] = {key: int(re.search(rf"\.{key}:\s+(\d+)", body).group(1)) for key in
+                seen[k] = {key: rec[key] for key in
                            ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")}
     assert sorted(seen) == ["surface_dist_bwd_kernel", "surface_dist_kernel"], sorted(seen)
     for name, m in sorted(seen.items()):

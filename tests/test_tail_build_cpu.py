@@ -5,17 +5,11 @@ the length of the dependent chain inside a workgroup, so a register spilled to s
 spilling `sdf_prep_kernel` once made the launch behind it fault (tests/test_build_cpu.py).  All three instantiations stay free of
 scratch, inside the 128 vector registers that two workgroups per CU leave a thread, and inside the 80 KB of LDS that two workgroups
 share at MANO's 248 weight segments.  The test reads the AMDGPU metadata records of the product build only."""
-import os
-import re
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "ihmr_amd", "csrc")
-# the product flags (ihmr_amd/hip.py: HIPCC_FLAGS) as a device-only assembly listing
-BASE = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}", "--cuda-device-only", "-S"]
+import codeobj
 
 pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not available")
 
@@ -28,23 +22,8 @@ def opt_tail_dynamic_lds(nseg):
     return 2 * nseg * 12 * 4
 
 
-def test_tail_kernel_forms_use_no_scratch_and_fit_two_per_cu(tmp_path):
-    out = tmp_path / "ihmr.s"
-    r = subprocess.run(BASE + ["-o", str(out), "ihmr_hip.hip"], cwd=SRC, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    text = out.read_text()
-    # one YAML record per kernel, keys sorted: `.group_segment_fixed_size` stands BEFORE `.name`, so a record is cut at its first and
-    # last key, not at `.name`
-    recs = re.findall(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", text, flags=re.S)
-    assert recs, "no kernel metadata records in the assembly"
-    seen = {}
-    for body in recs:
-        name = re.search(r"\.name:\s+(\S+)", body).group(1)
-        if not name.startswith("_Z15opt_tail_kernelILb"):
-            continue
-        get = lambda key: int(re.search(rf"\.{key}:\s+(\d+)", body).group(1))
-        seen[name] = {k: get(k) for k in ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
-                                          "group_segment_fixed_size")}
+def test_tail_kernel_forms_use_no_scratch_and_fit_two_per_cu():
+    seen = codeobj.matching("_Z15opt_tail_kernelILb")
     assert len(seen) == 3, sorted(seen)
     for name, m in sorted(seen.items()):
         lds = m["group_segment_fixed_size"] + opt_tail_dynamic_lds(NSEG)

@@ -13,9 +13,10 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import codeobj  # noqa: E402
+import hostbuild  # noqa: E402
 import volume_ref as VR  # noqa: E402
 
-SAN = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off", "-fno-fast-math"]
 DIFF_CAP = 1e-4          # share of the counted voxels on which the float32 and the float64 grids may differ
 
 
@@ -108,8 +109,7 @@ def test_close_boundary_closes_the_wrist(kind):
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     d = tmp_path_factory.mktemp("volume_pure")
-    exe = str(d / "volume_host_driver")
-    subprocess.check_call(["g++"] + SAN + [os.path.join(ROOT, "tests", "volume_host_driver.cpp"), "-o", exe])
+    exe = hostbuild.build("volume_host_driver.cpp", d)
     count = [0]
 
     def run(case, n):
@@ -120,8 +120,7 @@ def driver(tmp_path_factory):
             for v, f in ((case.va, case.fa), (case.vb, case.fb)):
                 fh.write(v.tobytes())
                 fh.write(f.tobytes())
-        r = subprocess.run([exe, fin, fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-        assert r.returncode == 0, r.stderr[-3000:]            # a sanitizer report is a non-zero exit
+        hostbuild.run(exe, fin, fout)
         raw = open(fout, "rb").read()
         T = n ** 3
         assert len(raw) == 16 + 4 + 4 * T + 4 * T * 1024
@@ -158,10 +157,7 @@ def test_column_range_clamp_and_record_packing(tmp_path):
                    '  int a, b, c, d; printf("%%d\\n", (int)vol_col_range(-500.f, 700.f, 3.f, 1e5f, -1e5f, 0.f, a, b, c, d)); printf("%%d %%d %%d %%d\\n", a, b, c, d);\n'
                    '  printf("%%d\\n", (int)vol_col_range(5.f, 7.f, 6.f, 0.f, 0.1f, 0.2f, a, b, c, d));\n'
                    '  return 0; }\n' % os.path.join(ROOT, "ihmr_amd", "csrc", "volume_pure.h"))
-    exe = str(tmp_path / "clamp")
-    subprocess.check_call(["g++"] + SAN + [str(src), "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    r = hostbuild.run(hostbuild.build(src, tmp_path))
     rows = [tuple(int(x) for x in line.split()) for line in r.stdout.strip().splitlines()]
     f = np.float32
     for x, (lo, hi) in zip([-3e38, -1e9, -100.0, -1.2, -1.0, 0.0, 0.97, 1.0, 1.2, 100.0, 1e9, 3e38], rows):
@@ -176,21 +172,15 @@ def test_column_range_clamp_and_record_packing(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the build
-def test_volume_kernels_use_no_scratch_and_the_symbol_is_exported(tmp_path):
+def test_volume_kernels_use_no_scratch_and_the_symbol_is_exported():
     import ctypes
 
     from ihmr_amd import hip
-    out = tmp_path / "ihmr.s"
-    cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", f"-I{os.path.join(ROOT, 'include')}",
-           "--cuda-device-only", "-S", "-o", str(out), "ihmr_hip.hip"]
-    r = subprocess.run(cmd, cwd=os.path.join(ROOT, "ihmr_amd", "csrc"), capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
     seen = {}
-    for body in re.findall(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", out.read_text(), flags=re.S):
-        name = re.search(r"\.name:\s+(\S+)", body).group(1)
+    for name, rec in codeobj.records().items():
         for k in ("vol_box_kernel", "vol_count_kernel"):
             if k in name:
-                seen[k] = {key: int(re.search(rf"\.{key}:\s+(\d+)", body).group(1)) for key in
+                seen[k] = {key: rec[key] for key in
                            ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")}
     assert sorted(seen) == ["vol_box_kernel", "vol_count_kernel"], sorted(seen)
     for name, m in sorted(seen.items()):
