@@ -321,9 +321,7 @@ def _mirror_to_left(m: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
     sgn = np.array([-1.0, 1.0, 1.0])
     pd = pd * (sgn[None, :, None, None, None] * sgn[None, None, :, None, None] * sgn[None, None, None, None, :])
     out["posedirs"] = pd.reshape(135, NUM_VERTS * 3)
-    hm = out["hands_mean"].reshape(15, 3).copy()
-    hm[:, 1:] *= -1
-    out["hands_mean"] = hm.reshape(45)
+    out["hands_mean"] = _mirror_pose_rows(out["hands_mean"])
     return out
 
 
@@ -392,6 +390,39 @@ def load_mano_pkl(path: str) -> Dict[str, np.ndarray]:
     )
     assert out["v_template"].shape == (NUM_VERTS, 3) and out["faces"].shape == (NUM_FACES, 3)
     return _as_f32(out)
+
+
+def _mirror_pose_rows(rows: np.ndarray) -> np.ndarray:
+    """(..., 45) axis-angle rows of the right hand -> the left hand's: the rule :func:`_mirror_to_left` applies to ``hands_mean``
+    (mirror across x: the y and z components of every joint's rotation vector change sign)."""
+    out = np.array(rows, copy=True).reshape(rows.shape[:-1] + (15, 3))
+    out[..., 1:] *= -1
+    return out.reshape(rows.shape)
+
+
+def synthetic_hand_components(is_rhand: bool = True, seed: int = 0) -> np.ndarray:
+    """Deterministic stand-in for MANO's ``hands_components``: (45,45) float32 with orthonormal rows (the Q factor of a seeded normal
+    matrix), the left hand's rows the mirror of the right's.  Drawn from a ``RandomState`` of its own, so no number of
+    :func:`synthetic_mano` depends on it."""
+    rng = np.random.RandomState(0x504341 + seed)          # "PCA"
+    q, r = np.linalg.qr(rng.standard_normal((45, 45)))
+    basis = (q * np.sign(np.diag(r))[None]).T             # sign-fixed: the factorisation is unique, whatever LAPACK returns
+    if not is_rhand:
+        basis = _mirror_pose_rows(basis)
+    return np.ascontiguousarray(basis, dtype=np.float32)
+
+
+def get_hand_components(model_path: str | None, is_rhand: bool, seed: int = 0) -> np.ndarray:
+    """``hands_components`` (45,45) float32, row k = PCA component k of the 45 hand-pose parameters (what ``smplx.create(...,
+    use_pca=True, num_pca_comps=K)`` cuts to its first K rows): read from the pkl when a real file exists, else the seeded synthetic
+    basis.  Kept apart from :func:`get_mano_arrays`, whose dict keeps exactly its keys."""
+    if model_path and osp.isfile(model_path):
+        with open(model_path, "rb") as f:
+            data = _TolerantUnpickler(io.BytesIO(f.read()), encoding="latin1").load()
+        comps = _to_array(data["hands_components"]).astype(np.float64)
+        assert comps.shape == (45, 45), comps.shape
+        return np.ascontiguousarray(comps, dtype=np.float32)
+    return synthetic_hand_components(is_rhand=is_rhand, seed=seed)
 
 
 def get_mano_arrays(model_path: str | None, is_rhand: bool, seed: int = 0) -> Dict[str, np.ndarray]:

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "ihmr_common.h"
+#include "../../include/ihmr_mano_ext.h"
 #include "mano_lbs.h"
 #include "sdf_collision.h"
 #include "preprocess.h"
@@ -23,6 +24,7 @@
 #include "evaluate.h"
 #include "volume.h"
 #include "surface.h"
+#include "mano_pose_space.h"
 #include "train.h"
 #include "train_conv.h"
 #include "copy_pack.h"
@@ -899,6 +901,27 @@ extern "C" int ihmr_surface_distance_bwd(const float* points, int P, const float
                           (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------------------------------ MANO layer: pose space and output stage
+// (include/ihmr_mano_ext.h)
+extern "C" int ihmr_mano_pca_fwd(const float* coeffs, const float* comps, int N, int K, float* pose45, void* stream) {
+    return mps_pca_fwd_launch(coeffs, comps, N, K, pose45, (hipStream_t)stream);
+}
+
+extern "C" int ihmr_mano_pca_bwd(const float* d_pose45, const float* comps, int N, int K, float* d_coeffs, void* stream) {
+    return mps_pca_bwd_launch(d_pose45, comps, N, K, d_coeffs, (hipStream_t)stream);
+}
+
+extern "C" int ihmr_mano_post_fwd(const float* verts_in, const float* joints16_in, const float* transl, const int32_t* tip_ids, int N,
+                                  float* verts_out, float* joints_out, void* stream) {
+    return mps_post_fwd_launch(verts_in, joints16_in, transl, tip_ids, N, verts_out, joints_out, (hipStream_t)stream);
+}
+
+extern "C" int ihmr_mano_post_bwd(const float* d_verts_out, const float* d_joints_out, const int32_t* tip_ids, int N, float* d_verts_in,
+                                  float* d_joints16, float* d_transl, void* stream) {
+    return mps_post_bwd_launch(d_verts_out, d_joints_out, tip_ids, N, d_verts_in, d_joints16, d_transl, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------ IHMR-MLP training gradient
 extern "C" int ihmr_mlp_train_grad(const ihmr_mano* m, const ihmr_mano* m_left, const ihmr_opt_io* io, int B,
                                    const ihmr_opt_weights* w, const ihmr_train_weights* tw, const float* gt_pose,
                                    const float* gt_shape, const float* params_weight, const float* init_shape,

@@ -224,13 +224,23 @@ SIGNATURES = {
     "ihmr_cast_f32_bf16": (_i, [_vp, _vp, _z, _vp]),
 }
 EXPORTED_SYMBOLS = list(SIGNATURES)      # every symbol include/ihmr_hip.h declares
+# The same for include/ihmr_mano_ext.h, the second public header (the MANO layer's pose space and output stage);
+# tests/test_mano_space_cpu.py compares it with that header's prototypes.  No name is in both tables.
+SIGNATURES_EXT = {
+    "ihmr_mano_pca_fwd": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "ihmr_mano_pca_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "ihmr_mano_post_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "ihmr_mano_post_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+}
+MANO_POSE_DIM = 45                       # include/ihmr_mano_ext.h: IHMR_MANO_POSE_DIM
 
 
-def bind(L):
-    """Give every function of SIGNATURES that the loaded library `L` exports its restype and argtypes.  One rule for a library
-    that lacks a symbol (an older build named with IHMR_HIP_LIBRARY for an A/B run against the parent commit): it is skipped, and
-    a call of it raises AttributeError.  The product library is checked for every symbol where it is built."""
-    for name, (restype, argtypes) in SIGNATURES.items():
+def bind(L, table=SIGNATURES):
+    """Give every function of `table` (SIGNATURES or SIGNATURES_EXT) that the loaded library `L` exports its restype and argtypes.
+    One rule for a library that lacks a symbol (an older build named with IHMR_HIP_LIBRARY for an A/B run against the parent
+    commit): it is skipped, and a call of it raises AttributeError.  The product library is checked for every symbol where it is
+    built."""
+    for name, (restype, argtypes) in table.items():
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -238,8 +248,9 @@ def bind(L):
 
 
 def sources():
+    include = osp.join(osp.dirname(_HERE), "include")
     return sorted(osp.join(SRC_DIR, f) for f in os.listdir(SRC_DIR) if f.endswith((".hip", ".h"))) + [
-        osp.join(osp.dirname(_HERE), "include", "ihmr_hip.h")]
+        osp.join(include, "ihmr_hip.h"), osp.join(include, "ihmr_mano_ext.h")]
 
 
 HASH_PATH = osp.join(_HERE, "libihmr_hip.srchash")
@@ -335,7 +346,7 @@ def lib():
     unavailable -- never falls back."""
     global _LIB
     if _LIB is None:
-        _LIB = bind(C.CDLL(_resolve_library()))
+        _LIB = bind(bind(C.CDLL(_resolve_library())), SIGNATURES_EXT)
     return _LIB
 
 
