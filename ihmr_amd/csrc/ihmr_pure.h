@@ -202,7 +202,10 @@ IHMR_PURE unsigned sdf_qcell_with_mask(unsigned c, unsigned m8) { return c | (m8
 IHMR_PURE unsigned sdf_qcell_mask(unsigned c) { return (c & SDF_QCELL_IN) ? ((c >> SDF_QCELL_MASK_SHIFT) & 0xffu) : 0u; }
 
 // Grid coordinates of the query vertex q against the box (cx, cy, cz, d.b) of the sampled hand, and whether its cell touches the grid at
-// all (false for a query completely outside, and for a non-finite one).  torch's grid_sample: x addresses the fastest axis.
+// all: false for a query completely outside, for a non-finite query and for a non-finite box.  A NaN anywhere makes a coordinate NaN, an
+// infinite query or centre makes it infinite or NaN, and every comparison below is then false; an infinite box SCALE with a finite centre
+// would send every finite query to the grid's centre (x / inf = 0), so it is refused by name ("Non-finite input").  The callers
+// convert ix, iy, iz to integers only behind in_grid: -1 <= floor <= 31 there.  torch's grid_sample: x addresses the fastest axis.
 struct SdfQuery { float ix, iy, iz; bool in_grid; };
 IHMR_PURE SdfQuery sdf_query_cell(float qx, float qy, float qz, float cx, float cy, float cz, const SdfDivisor& d, int swap_xz, int align_corners) {
     const float nx0 = sdf_div(qx - cx, d), nz0 = sdf_div(qz - cz, d);
@@ -211,7 +214,8 @@ IHMR_PURE SdfQuery sdf_query_cell(float qx, float qy, float qz, float cx, float 
     r.iy = sdf_unnorm(sdf_div(qy - cy, d), align_corners);
     r.iz = sdf_unnorm(swap_xz ? nx0 : nz0, align_corners);
     const float x0 = floorf(r.ix), y0 = floorf(r.iy), z0 = floorf(r.iz);
-    r.in_grid = x0 >= -1.0f && x0 <= (float)(SDF_G - 1) && y0 >= -1.0f && y0 <= (float)(SDF_G - 1) && z0 >= -1.0f && z0 <= (float)(SDF_G - 1);
+    r.in_grid = x0 >= -1.0f && x0 <= (float)(SDF_G - 1) && y0 >= -1.0f && y0 <= (float)(SDF_G - 1) && z0 >= -1.0f && z0 <= (float)(SDF_G - 1) &&
+                fabsf(d.b) < INFINITY;
     return r;
 }
 

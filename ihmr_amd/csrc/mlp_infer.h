@@ -115,7 +115,9 @@ __device__ __forceinline__ void mlpi_layer(const MlpHeadArgs& a, const ihmr_opt_
             if (orow < B && ocol < N) {
                 float v = s + a.b[LAYER][ocol];
                 if (LAYER < 3) {
-                    a.h[LAYER < 3 ? LAYER : 0][(size_t)orow * N + ocol] = fmaxf(v, 0.f);
+                    // ReLU that keeps a NaN, as torch's does (fmaxf alone returns 0 for it: a sample with a NaN feature would then be
+                    // evaluated on zero activations and could be kept; with the NaN its losses are NaN and the stage is rejected)
+                    a.h[LAYER < 3 ? LAYER : 0][(size_t)orow * N + ocol] = v != v ? v : fmaxf(v, 0.f);
                 } else {
                     const int e = (int)a.col[ocol];
                     v = a.prev[(size_t)orow * 122 + e] + v;       // new[:, COLS[n]] += res[:, o:o+k]

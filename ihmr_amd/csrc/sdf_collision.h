@@ -447,7 +447,8 @@ __global__ __launch_bounds__(PT, SDF_PREP_MIN_WAVES) void sdf_prep_kernel(VertLa
         if (!DENSE) {
             // completely outside the grid (or non-finite): contributes nothing
             const SdfQuery q = sdf_query_cell(oq[rep][0], oq[rep][1], oq[rep][2], cx, cy, cz, dsc, ws.swap_xz, ws.align_corners);
-            const int i0 = (int)floorf(q.ix), j0 = (int)floorf(q.iy), k0 = (int)floorf(q.iz);
+            // (converted only for an accepted query: -1 <= floor <= 31 there; a rejected one may hold NaN, +-inf or 1e30-scaled values)
+            const int i0 = q.in_grid ? (int)floorf(q.ix) : 0, j0 = q.in_grid ? (int)floorf(q.iy) : 0, k0 = q.in_grid ? (int)floorf(q.iz) : 0;
             // the query's cell for the fused sampler (entry hnd * 778 + v of sample b): parked in LDS; written to qcell at the end of
             // the kernel together with the inside mask of the cell's eight corners
             cellw[v] = sdf_qcell_pack(q.in_grid, i0, j0, k0);
@@ -490,7 +491,13 @@ __global__ __launch_bounds__(PT, SDF_PREP_MIN_WAVES) void sdf_prep_kernel(VertLa
         if (reuse) {
             float m = red_disp[0];
             for (int w = 1; w < PT / WAVE; ++w) m = fmaxf(m, red_disp[w]);
-            reuse = m <= SDF_LIST_SLACK - 1e-4f;        // (a NaN compares false: rebuild)
+            // (m is never NaN: the fmaxf that forms it drops a NaN displacement.  A hand with non-finite vertices therefore reports the
+            // displacement of its finite coordinates and may "reuse" its lists.  In this loop the vertices come from the LBS, where a
+            // non-finite parameter makes a whole coordinate axis of the hand non-finite (or all of it): every triangle then has a
+            // non-finite corner, no ray hits, the hand has no inside voxel and no work item -- the lists are kept and not read, and the
+            // reference pose and map stay those of the last finite pose, valid again if the hand returns to it.  A hand with only SOME
+            // non-finite vertices (seam B, which has no lists) does have inside voxels.  DESIGN.md, "Non-finite input")
+            reuse = m <= SDF_LIST_SLACK - 1e-4f;
             moved = m * 1.0001f + 1e-6f;
         }
         lists_reused = reuse;

@@ -88,6 +88,13 @@ int ihmr_sdf_collision(const int32_t* faces_right, const int32_t* faces_left, co
  * (The position of the voxel centres -- cell-centred, p = -1 + (2i+1)/32 -- is NOT switchable: the exact inside / outside
  * arithmetic of the ray test is derived for it.) */
 typedef struct ihmr_sdf_options { int align_corners; float loss_divisor; int swap_xz; } ihmr_sdf_options;
+/* NON-FINITE VERTICES (NaN, +-inf, coordinates whose extent overflows, a hand collapsed to one point) are legal input: the call
+ * returns 0, reads and writes only its own buffers, and sample b's rows of the four outputs are a function of sample b's vertices
+ * alone -- the other samples' rows are, byte for byte, those of a call in which sample b is an ordinary pair, and sample b's own rows
+ * are the same bytes on every call and at every batch position.  What those rows hold is decided by three rules (DESIGN.md,
+ * "Non-finite input"): a query vertex that is not finite, or that is sampled in a hand whose box (centre, scale) is not finite,
+ * reads no voxel (per_vert 0; origin_scale and dval 0 or NaN: they are multiplied by the box scale / its reciprocal); a triangle
+ * with a non-finite corner is never crossed by a ray; a voxel's distance is the minimum over the triangles with a finite distance. */
 int ihmr_sdf_collision_ex(const int32_t* faces_right, const int32_t* faces_left, const float* hand_verts, int B,
                           float robustifier, const ihmr_sdf_options* options, float* loss, float* per_vert, float* origin_scale,
                           float* dval, void* workspace, void* stream);
@@ -194,7 +201,16 @@ size_t ihmr_opt_workspace_bytes(int B);
  * faces for the collision term (loss_utils.py:34-38), NULL = use the right faces.
  * one stage of optimize() (:393-407): `n_iters` iterations of forward -> losses -> snapshot -> backward -> optimizer
  * step on the stage's parameter blocks.  Then (:377-387) filter + per-sample argmin of the select loss over the
- * snapshots, and write the selected parameters back. */
+ * snapshots, and write the selected parameters back.
+ * NON-FINITE INPUT.  A sample whose targets or parameters are, or become, NaN / +-inf stays inside its own rows: every output and
+ * state word of the other samples (parameters, optimizer state, snapshots, selection, vertices, joints, losses) is, byte for byte,
+ * that of a call in which the sample is ordinary, and the sample's own rows are the same bytes on every call and at every batch
+ * position.  Selection rule: snapshot 0 is the first candidate and snapshot s replaces the best so far only if its key (the select loss
+ * of a snapshot that passes every filter, 1e11 otherwise) is LESS than it -- a NaN key never wins, and a NaN select loss of snapshot
+ * 0 is never beaten (selected = 0: the sample leaves the stage with the parameters it entered with).  This is the reference's result
+ * except in one case: torch.argmin takes a NaN for the minimum, so where a later snapshot passes every filter with a NaN select loss
+ * -- possible only when the select loss itself carries no filter criterion -- the reference selects the first such snapshot and
+ * this library never does. */
 int ihmr_opt_run_stage(const ihmr_mano* m, const ihmr_mano* m_left, const ihmr_opt_io* io, int B,
                        const ihmr_opt_weights* w, const ihmr_opt_stage* stage, void* stream);
 /* forward() + __compute_loss(weights) only (:413-414), no step */
@@ -676,7 +692,10 @@ int ihmr_flush_kernel_timer(void);
  *                            vertex gradient (test() has no backward).
  * Weights: K-major [Kpad][ldw] as ihmr_conv_igemm takes them (layer 0: Kpad = 1152 rows, zeros beyond 1146).  Loss indices: IHMR_LOSS_*
  * (0 joints_2d_loss_p, 1 joints_3d_loss_p, 2 collision_loss).  workspace: ihmr_mlp_workspace_bytes(B) (the hidden activations).
- * All pointers device pointers. */
+ * All pointers device pointers.
+ * NON-FINITE INPUT: a NaN / inf in a sample's features, parameters or targets stays in that sample's rows (of the batch buffers and of
+ * the "prev" tables: the row of its dataset index).  The head's ReLU keeps a NaN as torch's does, every keep / reject comparison with a
+ * NaN is false, so such a sample keeps no stage's update (kept = 0) and its prev_final row stays its first evaluation's. */
 typedef struct ihmr_mlp_net { const float* w[4]; const float* b[4]; int ldw[4]; int k_out; int col[122]; } ihmr_mlp_net;
 typedef struct ihmr_mlp_tables {
     const int64_t* idx;        /* (B) dataset index of every batch row -- PRECONDITION: distinct within a batch (the reference's OptDataset gives
