@@ -22,6 +22,7 @@ from . import hip
 from . import mano as mano_shim
 from . import ry_utils
 from .baseline_train import BaselineTrainMixin
+from .export import ResultExporter
 from .networks import InterHandEncoder
 from .sdf import SDFLoss, refuse_training_robustifier
 
@@ -36,6 +37,11 @@ def batch_orthogonal_project(X, camera):
 
 class InterHandModel(BaselineTrainMixin):
     name = "InterHandModel"
+    # baseline_model.py:358-375: the export's keys in the order handed out; none of them is a constant made on the host
+    EXPORT_ORDER = ("pred_cam_params", "pred_hand_type", "pred_pose_params", "pred_shape_params", "pred_hand_trans",
+                    "gt_right_hand_verts", "gt_left_hand_verts", "pred_right_hand_verts", "pred_left_hand_verts", "mano_params_weight",
+                    "pred_joints_3d", "gt_joints_3d", "collision_loss_origin_scale", "do_flip")
+    EXPORT_HOST_KEYS = {}
 
     def __init__(self, opt):
         hip.require_gpu()
@@ -56,6 +62,7 @@ class InterHandModel(BaselineTrainMixin):
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.load_mean_params()
         self.load_mano_model()
+        self._exporter = ResultExporter(self.device)
         self.sdf_loss = SDFLoss(self.mano_models["right"].faces, self.mano_models["left"].faces, robustifier=None).to(self.device)
         self.encoder = InterHandEncoder(opt, self.mean_params).to(self.device)
         # test() as ONE hipGraph per instance (opt.use_test_graph, default on; as MLPModel.test()): ~150 launches whose dependent gaps
@@ -83,15 +90,7 @@ class InterHandModel(BaselineTrainMixin):
 
     # baseline_model.py:133-153
     def load_mano_model(self):
-        root = getattr(self.opt, "model_root", "") or ""
-        models = {}
-        for hand_type in ["left", "right"]:
-            f = osp.join(root, f"MANO_{hand_type.upper()}.pkl")
-            models[hand_type] = mano_shim.create(f, "mano", use_pca=False, is_rhand=(hand_type == "right"), batch_size=self.batch_size)
-        diff = torch.mean(torch.abs(models["left"].shapedirs[:, 0, :] - models["right"].shapedirs[:, 0, :]))
-        if diff < 1e-7:
-            models["left"].shapedirs[:, 0, :] *= -1
-        self.mano_models = {k: m.to(self.device) for k, m in models.items()}
+        self.mano_models = mano_shim.create_pair(getattr(self.opt, "model_root", ""), self.batch_size, self.device)
 
     def eval(self):
         self.encoder.eval()
@@ -195,26 +194,10 @@ class InterHandModel(BaselineTrainMixin):
 
     # baseline_model.py:358-375
     def get_pred_result(self):
-        return OrderedDict((k, v.detach().cpu().numpy()) for k, v in self._export_sources().items())
+        """Arrays the caller owns (:mod:`ihmr_amd.export` states the contract)."""
+        return self._exporter.blocking(self._export_sources(), self.EXPORT_HOST_KEYS, self.EXPORT_ORDER)
 
     def get_pred_result_async(self):
-        """``get_pred_result()`` without stalling the host (as :meth:`OptimizeModel.get_pred_result_async`): the copies are
-        queued behind ``test()`` on the current stream into pinned buffers (two alternating sets); ``wait()`` on the returned
-        handle blocks until they have landed.  The arrays are valid until the next-but-one export."""
-        if not hasattr(self, "_pinned"):
-            self._pinned, self._pin_slot = [None, None], 0
-        self._pin_slot ^= 1
-        src = OrderedDict((k, v.detach().contiguous()) for k, v in self._export_sources().items())
-        if self._pinned[self._pin_slot] is None:
-            self._pinned[self._pin_slot] = OrderedDict((k, torch.empty(v.shape, dtype=v.dtype, pin_memory=True)) for k, v in src.items())
-        dst = self._pinned[self._pin_slot]
-        for k, v in src.items():
-            dst[k].copy_(v, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-
-        class _Pending:
-            def wait(self_inner):
-                ev.synchronize()
-                return OrderedDict((k, v.numpy()) for k, v in dst.items())
-        return _Pending()
+        """``get_pred_result()`` without stalling the host (as :meth:`OptimizeModel.get_pred_result_async`): queued behind ``test()``
+        on the current stream; the arrays of the returned handle's ``wait()`` are valid until the next-but-one export, blocking ones counted."""
+        return self._exporter.start(self._export_sources(), self.EXPORT_HOST_KEYS, self.EXPORT_ORDER)

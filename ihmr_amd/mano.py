@@ -19,6 +19,7 @@ today's path: the same launches, the same bits, the 5-field ``ManoOutput``.
 """
 from __future__ import annotations
 
+import os.path as osp
 from collections import namedtuple
 
 import numpy as np
@@ -197,3 +198,14 @@ def create(model_path, model_type="mano", use_pca=False, num_pca_comps=6, flat_h
     comps = get_hand_components(model_path, is_rhand) if use_pca else None
     return MANO(get_mano_arrays(model_path, is_rhand), is_rhand=is_rhand, batch_size=batch_size, use_pca=use_pca,
                 num_pca_comps=num_pca_comps, flat_hand_mean=flat_hand_mean, hand_components=comps)
+
+
+def create_pair(model_root, batch_size, device):
+    """``{"left", "right"}`` models from ``MANO_{LEFT,RIGHT}.pkl`` under ``model_root``, as every model of the reference loads them
+    (optimize_model.py:97-117, baseline_model.py:133-153): a left hand whose first shape direction carries the right hand's x-sign
+    (the published files) is flipped."""
+    models = {hand_type: create(osp.join(model_root or "", f"MANO_{hand_type.upper()}.pkl"), "mano", use_pca=False,
+                                is_rhand=(hand_type == "right"), batch_size=batch_size) for hand_type in ("left", "right")}
+    if torch.mean(torch.abs(models["left"].shapedirs[:, 0, :] - models["right"].shapedirs[:, 0, :])) < 1e-7:
+        models["left"].shapedirs[:, 0, :] *= -1
+    return {k: m.to(device) for k, m in models.items()}

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import hip, two_hand
+from .export import ResultExporter
 from .networks import InterHandSubNetwork
 from .mlp_train import MLPTrainMixin
 from .optimize_model import OptimizeModel
@@ -38,6 +39,11 @@ LOSS_SLOT = dict(joints_2d_loss_p=0, joints_3d_loss_p=1, collision_loss=2)      
 
 class MLPModel(MLPTrainMixin):
     name = "InterHandModel"  # sic, mlp_model.py:26-27
+    # mlp_model.py:702-719: the export's keys in the order handed out, and the one that is a constant made on the host
+    EXPORT_ORDER = ("pred_cam_params", "pred_pose_params", "pred_shape_params", "pred_hand_trans", "gt_right_hand_verts", "gt_left_hand_verts",
+                    "pred_right_hand_verts", "pred_left_hand_verts", "mano_params_weight", "pred_joints_3d", "gt_joints_3d", "do_flip",
+                    "collision_loss", "collision_loss_origin_scale")
+    EXPORT_HOST_KEYS = dict(do_flip=0)
 
     def __init__(self, opt):
         hip.require_gpu()
@@ -49,6 +55,7 @@ class MLPModel(MLPTrainMixin):
         self._core = OptimizeModel(core_opt)           # buffers, MANO constants, fused forward + losses
         self.mano_models = self._core.mano_models
         self.device = self._core.device
+        self._exporter = ResultExporter(self.device)
         self.sub_network_list = []
         # mlp_model.py:219-231 -- only the three terms that drive the selection are evaluated at inference
         self.default_loss_weights = dict(joints_2d_loss=10.0, joints_3d_loss=10.0, collision_loss=1.0)
@@ -329,64 +336,11 @@ class MLPModel(MLPTrainMixin):
         self.pred_joints_2d = self._core.buf["joints_2d"]
         return render.current_visuals(self, idx)
 
-    _KEY_ORDER = ("pred_cam_params", "pred_pose_params", "pred_shape_params", "pred_hand_trans", "gt_right_hand_verts", "gt_left_hand_verts",
-                  "pred_right_hand_verts", "pred_left_hand_verts", "mano_params_weight", "pred_joints_3d", "gt_joints_3d", "do_flip",
-                  "collision_loss", "collision_loss_origin_scale")
-
-    # mlp_model.py:702-719
     def get_pred_result(self):
-        """Arrays the caller OWNS: the reference's loop keeps every batch's rows until it pickles them at the end (test_mlp.py:61-68,
-        evaluator.py:38-97 stores row views), so the synchronous export copies out of the two alternating pinned buffers the
-        asynchronous one hands out views of."""
-        return OrderedDict((k, np.array(v, copy=True)) for k, v in self.get_pred_result_async().wait().items())
-
-    def _packed_export(self, src):
-        """The export's 13 tensors gathered into ONE device buffer by one launch (``ihmr_copy_segments``) and sent to the host in ONE
-        copy (round 4: 13 copies); returns the pinned host buffer and the (offset, shape, dtype) of every key in it."""
-        if not hasattr(self, "_pinned"):
-            self._pinned, self._pin_slot, self._pack_dev, self._pack_layout = [None, None], 0, None, None
-        layout, off = OrderedDict(), 0
-        for k, v in src.items():
-            layout[k] = (off, tuple(v.shape), v.dtype)
-            off += (v.numel() * v.element_size() + 15) // 16 * 16
-        if self._pack_dev is None or self._pack_dev.numel() < off or self._pack_layout != layout:
-            self._pack_dev = torch.empty(off, dtype=torch.uint8, device=self.device)
-            self._pinned, self._pack_layout = [None, None], layout
-        self._pin_slot ^= 1
-        if self._pinned[self._pin_slot] is None:
-            self._pinned[self._pin_slot] = torch.empty(off, dtype=torch.uint8, pin_memory=True)
-        pairs = []
-        for k, v in src.items():
-            o, shape, dt = layout[k]
-            dst = self._pack_dev[o:o + v.numel() * v.element_size()].view(dt).view(shape)
-            v = v.detach()
-            if not v.is_contiguous():
-                if v.dim() == 2 and v.stride(1) == 1:
-                    pass                                  # a column slice of the packed parameter matrix: a strided segment
-                else:
-                    v = v.contiguous()
-            pairs.append((v, dst))
-        hip.copy_segments(pairs)
-        host = self._pinned[self._pin_slot]
-        host.copy_(self._pack_dev[:host.numel()], non_blocking=True)
-        return host, layout
+        """Arrays the caller owns (:mod:`ihmr_amd.export` states the contract)."""
+        return self._exporter.blocking(self._export_sources(), self.EXPORT_HOST_KEYS, self.EXPORT_ORDER)
 
     def get_pred_result_async(self):
-        """``get_pred_result()`` without stalling the host (as :meth:`OptimizeModel.get_pred_result_async`): the copies are
-        queued behind ``test()`` on the current stream into pinned buffers (two alternating sets); ``wait()`` on the
-        returned handle blocks until they have landed.  The arrays are valid until the next-but-one export."""
-        host, layout = self._packed_export(self._export_sources())
-        ev = torch.cuda.Event()
-        ev.record()
-        model = self
-
-        class _Pending:
-            def wait(self_inner):
-                ev.synchronize()
-                out = {}
-                for k, (o, shape, dt) in layout.items():
-                    n = int(np.prod(shape)) * torch.empty((), dtype=dt).element_size()
-                    out[k] = host[o:o + n].view(dt).view(shape).numpy()
-                out["do_flip"] = np.zeros(model.batch_size).astype(np.int32)
-                return OrderedDict((k, out[k]) for k in model._KEY_ORDER)
-        return _Pending()
+        """``get_pred_result()`` without stalling the host (as :meth:`OptimizeModel.get_pred_result_async`): queued behind ``test()``
+        on the current stream; the arrays of the returned handle's ``wait()`` are valid until the next-but-one export, blocking ones counted."""
+        return self._exporter.start(self._export_sources(), self.EXPORT_HOST_KEYS, self.EXPORT_ORDER)

@@ -17,7 +17,6 @@ GPU->CPU bounce like the reference's ``_finger_reg_loss`` (``loss_utils.py:155,1
 from __future__ import annotations
 
 import ctypes as C
-import os.path as osp
 import sys
 from collections import OrderedDict
 
@@ -26,6 +25,7 @@ import torch
 
 from . import hip
 from . import mano as mano_shim
+from .export import ResultExporter
 from .strategies import OPT_DEFAULT_LOSS_WEIGHTS, get_strategy
 
 def _filter_factor(criterion: str) -> float:
@@ -81,22 +81,13 @@ def _weights(w) -> hip.OptWeights:
                           w["collision_loss_weight"], w["finger_reg_loss_weight"])
 
 
-class _PendingResult:
-    """Handle of :meth:`OptimizeModel.get_pred_result_async`."""
-
-    def __init__(self, pinned, event, batch_size):
-        self._pinned, self._event, self._n = pinned, event, batch_size
-
-    def wait(self):
-        self._event.synchronize()
-        out = OrderedDict((k, v.numpy()) for k, v in self._pinned.items())
-        out["do_flip"] = np.zeros(self._n).astype(np.int32)
-        out["pred_hand_type"] = np.ones(self._n).astype(np.int32)
-        return out
-
-
 class OptimizeModel:
     name = "OptimizeModel"
+    # optimize_model.py:418-435: the export's keys in the order handed out, and the ones that are constants made on the host
+    EXPORT_ORDER = ("pred_cam_params", "pred_hand_trans", "pred_shape_params", "pred_pose_params", "pred_right_hand_verts",
+                    "pred_left_hand_verts", "mano_params_weight", "pred_joints_3d", "gt_joints_3d", "collision_loss",
+                    "collision_loss_origin_scale", "do_flip", "pred_hand_type")
+    EXPORT_HOST_KEYS = dict(do_flip=0, pred_hand_type=1)
 
     def __init__(self, opt):
         hip.require_gpu()
@@ -112,6 +103,7 @@ class OptimizeModel:
         self.optimizer = getattr(opt, "optimizer", "adam")
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.load_mano_model()
+        self._exporter = ResultExporter(self.device)
         epoch = getattr(opt, "opt_epoch", None)
         self.strategy = get_strategy(opt.strategy, epoch)
         self.default_loss_weights = dict(OPT_DEFAULT_LOSS_WEIGHTS)
@@ -124,16 +116,7 @@ class OptimizeModel:
 
     # optimize_model.py:97-117
     def load_mano_model(self):
-        root = getattr(self.opt, "model_root", "") or ""
-        models = {}
-        for hand_type in ["left", "right"]:
-            f = osp.join(root, f"MANO_{hand_type.upper()}.pkl")
-            models[hand_type] = mano_shim.create(f, "mano", use_pca=False, is_rhand=(hand_type == "right"),
-                                                 batch_size=self.batch_size * 2)
-        diff = torch.mean(torch.abs(models["left"].shapedirs[:, 0, :] - models["right"].shapedirs[:, 0, :]))
-        if diff < 1e-7:
-            models["left"].shapedirs[:, 0, :] *= -1
-        self.mano_models = {k: m.to(self.device) for k, m in models.items()}
+        self.mano_models = mano_shim.create_pair(getattr(self.opt, "model_root", ""), self.batch_size * 2, self.device)
 
     def _alloc(self, B):
         dev = self.device
@@ -330,9 +313,10 @@ class OptimizeModel:
     def joints_2d_loss_p_batch(self): return self.buf["loss_batch"][0]
 
     def _export_sources(self):
+        b = self.buf     # the shape and pose arrays are laid side by side by the export itself (the properties' torch.cat without its kernels)
         return OrderedDict(
             pred_cam_params=self.pred_cam_params, pred_hand_trans=self.pred_hand_trans,
-            pred_shape_params=self.pred_shape_params, pred_pose_params=self.pred_pose_params,
+            pred_shape_params=(b["shape"][0], b["shape"][1]), pred_pose_params=(b["orient"][0], b["pose"][0], b["orient"][1], b["pose"][1]),
             pred_right_hand_verts=self.pred_right_hand_verts, pred_left_hand_verts=self.pred_left_hand_verts,
             mano_params_weight=self.mano_params_weight, pred_joints_3d=self.pred_joints_3d,
             gt_joints_3d=self.buf["gt_joints_3d"], collision_loss=self.collision_loss_batch,
@@ -340,29 +324,14 @@ class OptimizeModel:
 
     # optimize_model.py:418-435
     def get_pred_result(self):
-        n = lambda t: t.detach().cpu().numpy()
-        out = OrderedDict((k, n(v)) for k, v in self._export_sources().items())
-        out["do_flip"] = np.zeros(self.batch_size).astype(np.int32)
-        out["pred_hand_type"] = np.ones(self.batch_size).astype(np.int32)
-        return out
+        """Arrays the caller owns (:mod:`ihmr_amd.export` states the contract)."""
+        return self._exporter.blocking(self._export_sources(), self.EXPORT_HOST_KEYS, self.EXPORT_ORDER)
 
     def get_pred_result_async(self):
-        """``get_pred_result()`` without stalling the host: the device-to-host copies go, on the current stream and behind
-        the refinement that produced the values, into pinned host buffers (two alternating sets per instance); the
-        returned handle's ``wait()`` blocks until they have landed and hands out the same OrderedDict.  The arrays
-        are views of the pinned buffers: valid until the next-but-one export of this instance."""
-        if not hasattr(self, "_pinned"):
-            self._pinned, self._pin_slot = [None, None], 0
-        self._pin_slot ^= 1
-        src = self._export_sources()
-        if self._pinned[self._pin_slot] is None:
-            self._pinned[self._pin_slot] = OrderedDict((k, torch.empty(v.shape, dtype=v.dtype, pin_memory=True)) for k, v in src.items())
-        dst = self._pinned[self._pin_slot]
-        for k, v in src.items():
-            dst[k].copy_(v, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return _PendingResult(dst, ev, self.batch_size)
+        """``get_pred_result()`` without stalling the host: queued on the current stream behind the refinement that produced the
+        values; ``wait()`` on the returned handle blocks until they have landed.  The arrays are views of pinned memory, valid until
+        the next-but-one export of this instance (a blocking ``get_pred_result()`` counts as one)."""
+        return self._exporter.start(self._export_sources(), self.EXPORT_HOST_KEYS, self.EXPORT_ORDER)
 
     # optimize_model.py:437-455 (means of the per-sample values)
     def get_current_errors(self):
